@@ -5,6 +5,16 @@ Metric (BASELINE.json): device-resident encode+decode GB/s of input bytes
 (original_count * buffer_bytes per object, the reference's own formula,
 tests/benchmark.cpp:521-524).
 
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does what the headline
+figure needs and no more: it builds the buffer sets, checks one round trip,
+warms up, times the N steps of --mode and prints the line (metric, value, unit,
+ms_per_step = milliseconds per timed step, and the workload).  --dump-outputs
+DIR then also writes what the last timed step computed (dump_last_step).
+Everything else described below -- the other modes, the roofline legs,
+configs[4], the secondary and breadth shapes, the host-memory rates and the
+CPU baseline -- runs only with --full, which prints the same line with those
+legs added.
+
 Headline workload (configs[1]): 128 originals + 128 recovery pieces of 65536
 bytes, GF(2^8).  One *step* = one pass over OBJECTS independent objects
 (default 64, a storage node's stripes): each is encoded and then decoded with
@@ -67,6 +77,7 @@ REPO = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, REPO)
 
 HBM_PEAK_GBPS = 8000.0  # MI355X HBM3E spec (MI355X_MICROARCH.md)
+RAMP_S = 0.1  # a plain run's untimed clock ramp before its warm-up steps (headline)
 VP = ctypes.c_void_p
 
 # Benchmarks.md:8-27 (reference, "few year old laptop", AVX2, B = 2560 except 128+128 at 64000),
@@ -103,6 +114,11 @@ def parse():
                     help="batch mode: consecutive steps alternate over this many streams")
     ap.add_argument("--sharded-steps", type=int, default=0, help="steps of the configs[4] object (0 = min(steps, 10))")
     ap.add_argument("--no-sharded", action="store_true", help="skip the configs[4] sharded object")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline run: the other modes, the roofline legs, configs[4], the secondary and "
+                         "breadth shapes, the host-memory rates and the CPU baseline (each --no-* switch drops one)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=5.0)
     ap.add_argument("--no-secondary", action="store_true", help="skip 1000+200, B=64000 and the breadth shapes")
@@ -220,6 +236,49 @@ class Sets:
         self.n = nsets
 
 
+DUMP_LIMIT = 64_000_000  # bytes written by --dump-outputs, all files together
+
+
+def dump_positions(nbytes, objects):
+    """The byte positions --dump-outputs samples of an object's `nbytes` output
+    bytes (ascending; all of them where they fit): 24 MiB of float32 per array
+    over its objects, drawn from a fixed seed."""
+    import numpy as np
+    npos = (24 << 20) // (4 * objects)
+    if npos >= nbytes:
+        return np.arange(nbytes, dtype=np.int64)
+    return np.sort(np.random.default_rng(2024).integers(0, nbytes, npos))
+
+
+def dump_last_step(torch, path, sets, ids, rank, world):
+    """--dump-outputs: what a caller of the timed path holds after its last
+    step, for that step's objects (buffer sets `ids`, in step order): the R
+    recovery pieces every encode wrote ("recovery") and the K originals every
+    decode rebuilt ("decoded").  Whole, these are too large to keep, so each is
+    written twice: <name>.npy, float32 [objects, P], the bytes at P byte
+    positions of the object's pieces (row-major), drawn once from a fixed seed
+    and the same for every object and run; and <name>_sums.npy, float64
+    [objects, pieces], the sum of each piece's bytes (every byte counts in one).
+    The inputs are counter hashes of fixed seeds, so two runs with the same
+    arguments write the same files."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    suffix = "" if world == 1 else f"_rank{rank}"
+    nbytes = sets.nbytes
+    device = sets.orig[0].device
+    out = {}
+    for name, bufs, rows in (("recovery", sets.enc_work, sets.r), ("decoded", sets.dec_work, sets.k)):
+        idx = torch.from_numpy(dump_positions(rows * nbytes, len(ids))).to(device)
+        out[name] = torch.stack([bufs[i].view(-1).index_select(0, idx) for i in ids]).cpu().numpy().astype(np.float32)
+        out[name + "_sums"] = torch.stack([bufs[i][:rows].sum(dim=1, dtype=torch.int64)
+                                           for i in ids]).cpu().numpy().astype(np.float64)
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_LIMIT, f"--dump-outputs would write {total} bytes: fewer --objects"
+    for name, a in out.items():
+        np.save(os.path.join(path, name + suffix + ".npy"), a)
+    return {"dir": path, "files": sorted(n + suffix + ".npy" for n in out), "bytes": total, "objects": len(ids)}
+
+
 def main():
     args = parse()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -261,7 +320,42 @@ def main():
         if world > 1:
             dist.barrier()
 
-    head = headline(args, leo, torch, device, barrier, world, max_over_ranks)
+    head = headline(args, leo, torch, device, barrier, rank, world, max_over_ranks)
+
+    k, r, nbytes = args.K, args.R, args.bytes
+    line = {
+        "metric": "device-resident encode+decode GB/s (input bytes/s) at 128+128 and 32768+32768 pieces",
+        "value": head["value"],
+        "unit": "GB/s",
+        "n_gpus": n_devices,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": head["ms_per_step"],
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u8",
+        "data": "synthetic (counter-hash bytes on device)",
+    }
+    if args.dump_outputs:
+        line["dump_outputs"] = head["dumped"]
+    workload = (f"configs[1]: {k}+{r} x {nbytes} B pieces, GF(2^8); step = {args.objects} objects "
+                f"per rank, each encoded then decoded with all {k} originals lost, "
+                + (f"batched encode + decode launches of {head['launch_objects']} objects, "
+                   f"consecutive launch pairs on {args.batch_streams} streams"
+                   if args.mode == "batch" else f"{head['streams']} objects in flight")
+                + f"; {head['sets']} rotating buffer sets")
+    config = {"original_count": k, "recovery_count": r, "buffer_bytes": nbytes, "losses": k,
+              "objects_per_step": args.objects, "objects_per_launch": head["launch_objects"], "mode": args.mode,
+              "field": "FF8" if leo.leo_decode_work_count(k, r) <= 256 else "FF16",
+              "world": world, "devices": ",".join(f"{h}:{g}" for h, g in placement),
+              "shared_devices": n_devices < world}
+    if not args.full:  # the headline run alone
+        if rank == 0:
+            print(json.dumps({**line, "full": False, "config": {"workload": workload, **config}}), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     sharded = None
     if not args.no_sharded:
@@ -282,7 +376,6 @@ def main():
         cpu = cpu_baseline(args.K, args.R, args.bytes, args.cpu_seconds)
 
     if rank == 0:
-        k, r, nbytes = args.K, args.R, args.bytes
         batch = args.mode == "batch"
         kern1 = kernels_for(k, r, nbytes, k)
         traffic = pmc_traffic(head["dominant"][0], k, r, nbytes, head["launch_objects"] if batch else 1,
@@ -294,18 +387,7 @@ def main():
         kname = ("k_ff8_bs_slab<1> / <2>: %d-object encode-batch / decode-batch launches (bit-sliced tile; "
                  "dense encode form / full-loss decode form)" % head["launch_objects"]) if batch else kind
         out = {
-            "metric": "device-resident encode+decode GB/s (input bytes/s) at 128+128 and 32768+32768 pieces",
-            "value": head["value"],
-            "unit": "GB/s",
-            "n_gpus": n_devices,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": head["ms_per_step"],
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u8",
-            "data": "synthetic (counter-hash bytes on device)",
+            **line,
             # the secondary configs' times / roofline fractions and the PCIe-inclusive host rate as
             # top-level scalars (a record that keeps the head of the line or drops nested objects
             # still has them); the same figures sit in `roofline`, `host_e2e` and `secondary`
@@ -313,23 +395,15 @@ def main():
             **({"breadth_100x10_decode_us": breadth[0]["decode_us"]} if breadth else {}),
             "host_e2e_GBps": host["value"] if host else None,
             "host_encode_GBps": host["encode_GBps"] if host else None,
-            "config": {"workload": f"configs[1]: {k}+{r} x {nbytes} B pieces, GF(2^8); step = {args.objects} objects "
-                                   f"per rank, each encoded then decoded with all {k} originals lost, "
-                                   + (f"batched encode + decode launches of {head['launch_objects']} objects, "
-                                      f"consecutive launch pairs on {args.batch_streams} streams"
-                                      if args.mode == "batch" else f"{head['streams']} objects in flight")
-                                   + f"; {head['sets']} rotating buffer sets"
+            "full": True,
+            "config": {"workload": workload
                                    + (f"; plus configs[4] (sharded_object): one 32768+32768 x 65536 B object "
                                       f"column-sharded over {world} rank(s) on {n_devices} GPU(s)" if sharded else ""),
-                       "original_count": k, "recovery_count": r, "buffer_bytes": nbytes, "losses": k,
-                       "objects_per_step": args.objects, "objects_per_launch": head["launch_objects"], "mode": args.mode,
-                       "field": "FF8" if leo.leo_decode_work_count(k, r) <= 256 else "FF16",
+                       **config,
                        "sharding": "objects per rank (headline); 64-byte column blocks per rank (sharded_object); "
                                    "no collective",
-                       # scalars the driver's record keeps (it drops nested objects): ranks and their devices,
-                       # and the PCIe-inclusive host rate (never `value`)
-                       "world": world, "devices": ",".join(f"{h}:{g}" for h, g in placement),
-                       "shared_devices": n_devices < world,
+                       # scalars the driver's record keeps (it drops nested objects): ranks and their devices
+                       # (in `config` above), and the PCIe-inclusive host rate (never `value`)
                        "host_e2e_GBps": host["value"] if host else None,
                        "host_encode_GBps": host["encode_GBps"] if host else None,
                        "host_decode_GBps": host["decode_GBps"] if host else None,
@@ -403,7 +477,9 @@ def config_fracs(secondary, sharded, world):
     return out
 
 
-def headline(args, leo, torch, device, barrier, world, max_over_ranks):
+def headline(args, leo, torch, device, barrier, rank, world, max_over_ranks):
+    """The headline workload.  A plain run times --mode alone; --full also
+    times the other modes and the single calls (the roofline's legs)."""
     lib = leo.lib
     stream = torch.cuda.current_stream(device)
     k, r, nbytes = args.K, args.R, args.bytes
@@ -449,9 +525,10 @@ def headline(args, leo, torch, device, barrier, world, max_over_ranks):
     # arrays are built once per distinct group.
     PP = ctypes.POINTER(VP)
     nbatches = sets.n // lobj if sets.n % lobj == 0 else sets.n
-    batches = []
+    batches, batch_ids = [], []
     for bi in range(nbatches):
         ids = [(bi * lobj + o) % sets.n for o in range(lobj)]
+        batch_ids.append(ids)
         mk = lambda arrs: (PP * len(arrs))(*[ctypes.cast(a, PP) for a in arrs])  # noqa: E731
         batches.append((mk([sets.p_orig[i] for i in ids]), mk([sets.p_encw[i] for i in ids]),
                         mk([sets.p_null[i] for i in ids]), mk([sets.p_rec[i] for i in ids]),
@@ -504,13 +581,46 @@ def headline(args, leo, torch, device, barrier, world, max_over_ranks):
     for o in range(args.objects):
         i = o % sets.n
         assert torch.equal(sets.dec_work[i][:k], sets.orig[i]), "batch decode mismatch"
-    elapsed_calls = timed(run_calls, nstreams)
-    elapsed_serial = timed(run_calls, 1)
-    # the headline's launch events: allocated before the timed region, read after it
-    batch_ev = [torch.cuda.Event(enable_timing=True) for _ in range(4 * args.steps * groups)]
-    elapsed_batch = timed(run_batches, 1, batch_ev)
-    elapsed = elapsed_batch if args.mode == "batch" else elapsed_calls
+    batch = args.mode == "batch"
+    if not args.full:
+        # With --full the timed run of --mode comes behind the other modes' runs, which leave the
+        # GPU at its sustained clocks; a plain run gets there by running the mode's own steps,
+        # untimed, for RAMP_S before the warm-up (from idle, the first steps run at lower clocks).
+        t0 = time.perf_counter()
+        while time.perf_counter() - t0 < RAMP_S:
+            if batch:
+                run_batches(4, 1)
+            else:
+                run_calls(4, nstreams)
+            torch.cuda.synchronize()
+    elapsed_calls = elapsed_serial = elapsed_batch = None
+    if args.full or not batch:
+        elapsed_calls = timed(run_calls, nstreams)
+    if args.full:
+        elapsed_serial = timed(run_calls, 1)
+    if args.full or batch:
+        # the headline's launch events: allocated before the timed region, read after it (--full;
+        # a plain run records them too, so that both time the same path)
+        batch_ev = [torch.cuda.Event(enable_timing=True) for _ in range(4 * args.steps * groups)]
+        elapsed_batch = timed(run_batches, 1, batch_ev)
+    elapsed = elapsed_batch if batch else elapsed_calls
     leo.set_stream(stream.cuda_stream)
+    in_step = k * nbytes * args.objects
+    res = {"value": round(world * in_step * args.steps / elapsed / 1e9, 3),
+           "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+           "sets": sets.n, "streams": nstreams, "launch_objects": lobj}
+    if args.dump_outputs:  # the buffer sets of the last timed step, as the timed mode walks them
+        s = args.steps - 1
+        if batch:
+            ids = [i for g in range(groups)
+                   for i in batch_ids[(s * args.objects // lobj + g) % nbatches][:min(lobj, args.objects - g * lobj)]]
+        else:
+            ids = [(s * args.objects + o) % sets.n for o in range(args.objects)]
+        res["dumped"] = dump_last_step(torch, args.dump_outputs, sets, ids, rank, world)
+    if not args.full:
+        del sets
+        torch.cuda.empty_cache()
+        return res
 
     # Per-launch kernel duration with HIP events on the launch stream: a spin
     # kernel holds the stream while the host enqueues n back-to-back calls (one
@@ -560,14 +670,12 @@ def headline(args, leo, torch, device, barrier, world, max_over_ranks):
         dominant, single_dominant = batch_dominant, dominant
     else:
         single_dominant = dominant
-    in_step = k * nbytes * args.objects
 
     def rate(el, note):
         return {"value": round(world * in_step * args.steps / el / 1e9, 3),
                 "ms_per_step": round(el / args.steps * 1e3, 4), "note": note}
 
-    res = {"value": round(world * in_step * args.steps / elapsed / 1e9, 3),
-           "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+    res.update({
            "modes": {
                "batch": rate(elapsed_batch, f"leo_amd_encode_batch + leo_amd_decode_batch per {lobj} objects "
                                             f"(one launch each), {groups} launch pairs per step, consecutive pairs "
@@ -578,7 +686,7 @@ def headline(args, leo, torch, device, barrier, world, max_over_ranks):
                                               "waits for the previous (a plain drop-in caller)")},
            "t_enc": t_enc, "t_dec": t_dec, "tb_enc": tb_enc, "tb_dec": tb_dec,
            "span_enc": span_enc, "span_dec": span_dec, "dominant": dominant,
-           "single_dominant": single_dominant, "sets": sets.n, "streams": nstreams, "launch_objects": lobj}
+           "single_dominant": single_dominant})
     del sets
     torch.cuda.empty_cache()
     return res

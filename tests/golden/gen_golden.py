@@ -17,6 +17,9 @@ and stores only inputs' seeds and outputs:
                      ("hash_digests": oracle_lib.hash_bytes, seed 7, which the GPU
                      tests regenerate on the device in milliseconds).
 
+* golden_direct.npz  (--direct) the reference's outputs and GF(2^8) tables for the
+                     tests that otherwise need the compiled library itself.
+
 Input convention: piece i, byte j = low 8 bits of the (i*B + j)-th PCG32 output
 after PCGRandom.Seed(seed, trial) -- seed 2 as in tests/benchmark.cpp:53.
 
@@ -62,12 +65,18 @@ def main():
     ap.add_argument("--big", action="store_true", help="also digest the BASELINE shapes (needs ~10 GB RAM)")
     ap.add_argument("--big-decode", action="store_true",
                     help="only add the decoder digests at the BASELINE shapes to golden_digests.json")
+    ap.add_argument("--direct", action="store_true",
+                    help="only write golden_direct.npz: the reference's outputs on the inputs of "
+                         "test_oracle_vs_compiled_reference, and its GF(2^8) tables")
     args = ap.parse_args()
     ref = ol.reference()
     if ref is None:
         sys.exit("build the reference first: make -C oracle ref")
     if args.big_decode:
         big_decode(ref)
+        return
+    if args.direct:
+        direct(ref)
         return
 
     out = {}
@@ -105,6 +114,26 @@ def main():
             json.dump({"convention": "sha256 of recovery pieces 0..R-1 concatenated; inputs pcg_bytes(2,0,K,B) "
                                      "for 'digests', hash_bytes(7,K,B) for 'hash_digests'",
                        "digests": dig, "hash_digests": hdig}, f, indent=1)
+
+
+def direct(ref):
+    """golden_direct.npz: what the tests that drive the compiled reference
+    directly read from it, so that they also run where it is not compiled:
+    enc_ / dec_ / lo_<K>_<R>_<B> = its recovery pieces, the originals it rebuilds
+    (in loss order) and the lost originals for oracle_lib.direct_case(K, R, B);
+    ff8_log / ff8_exp / ff8_skew = its GF(2^8) tables after leo_init."""
+    import ctypes
+    out = {}
+    for (k, r, b) in ol.DIRECT_SHAPES:
+        data, junk, lo, lr = ol.direct_case(k, r, b)
+        res = ref.decode(data, junk, lo, lr)
+        out["enc_" + key(k, r, b)] = ref.encode(data, r)
+        out["dec_" + key(k, r, b)] = np.stack([res[i] for i in lo])
+        out["lo_" + key(k, r, b)] = np.array(lo, dtype=np.int32)
+    for name, (symbol, count) in ol.REF_FF8_TABLES.items():
+        out[name] = ol.reference_static_table(symbol, count, ctypes.c_uint8)
+        assert out[name] is not None, "nm is needed to find the reference's tables"
+    np.savez_compressed(os.path.join(HERE, "golden_direct.npz"), **out)
 
 
 def big_decode(ref):

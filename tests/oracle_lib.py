@@ -143,6 +143,46 @@ def reference() -> CpuCodec | None:
     return _ref
 
 
+def reference_static_table(name, count, dtype):
+    """A static table of the compiled reference, located through the symbol
+    table (the library's own leo_init_ anchors the load address); None where
+    the reference or nm is not available."""
+    import shutil
+    ref = reference()
+    nm = shutil.which("nm")
+    if ref is None or nm is None:
+        return None
+    syms = {}
+    for line in subprocess.run([nm, REF_SO], check=True, capture_output=True, text=True).stdout.splitlines():
+        p = line.split()
+        if len(p) == 3:
+            syms[p[2]] = int(p[0], 16)
+    base = ctypes.cast(ref.lib.leo_init_, ctypes.c_void_p).value - syms["leo_init_"]
+    return np.ctypeslib.as_array((dtype * count).from_address(base + syms[name])).copy()
+
+
+# The reference's GF(2^8) LogLUT / ExpLUT / FFTSkew (LeopardFF8.cpp:136-194, 496-531), which it
+# builds in leo_init: mangled names of its static arrays, and their lengths
+REF_FF8_TABLES = {"ff8_log": ("_ZN7leopard3ff8L6LogLUTE", 256), "ff8_exp": ("_ZN7leopard3ff8L6ExpLUTE", 256),
+                  "ff8_skew": ("_ZN7leopard3ff8L7FFTSkewE", 255)}
+
+# test_cpu_oracle.test_oracle_vs_compiled_reference: (K, R, B)
+DIRECT_SHAPES = [(2, 2, 64), (77, 31, 128), (128, 128, 64), (200, 56, 64), (129, 100, 64),
+                 (1000, 500, 64), (3000, 1, 64), (1, 1, 64)]
+
+
+def direct_case(k, r, b):
+    """Inputs of one DIRECT_SHAPES case: originals, non-codeword "recovery"
+    pieces, and which originals / recovery pieces are lost."""
+    rng = np.random.default_rng(k * 1000 + r)
+    data = rng.integers(0, 256, (k, b), dtype=np.uint8)
+    junk = rng.integers(0, 256, (r, b), dtype=np.uint8)
+    loss = min(r, k)
+    lo = sorted(rng.choice(k, loss, replace=False).tolist())
+    lr = sorted(rng.choice(r, r - loss, replace=False).tolist())
+    return data, junk, lo, lr
+
+
 # ---------------------------------------------------------------------------
 # The reference benchmark's synthetic data (tests/benchmark.cpp)
 

@@ -78,34 +78,17 @@ def test_multiply_matrices_are_the_field_multiply(const_tables):
             assert y == _mul(log, exp, x, c), (x, c)
 
 
-def _ref_static_table(name, count, dtype):
-    """A static table of the compiled reference, located through the symbol
-    table (the library's own leo_init_ anchors the load address)."""
-    so = ol.REF_SO
-    nm = shutil.which("nm")
-    if nm is None or not os.path.exists(so):
-        pytest.skip("compiled reference (oracle/_ref) or nm not available")
-    syms = {}
-    for line in subprocess.run([nm, so], check=True, capture_output=True, text=True).stdout.splitlines():
-        p = line.split()
-        if len(p) == 3:
-            syms[p[2]] = int(p[0], 16)
-    ref = ol.reference()
-    assert ref is not None
-    base = ctypes.cast(ref.lib.leo_init_, ctypes.c_void_p).value - syms["leo_init_"]
-    addr = base + syms[name]
-    return np.ctypeslib.as_array((dtype * count).from_address(addr)).copy()
-
-
 def test_tables_match_the_compiled_reference(const_tables):
+    """Against the tables the compiled reference built in leo_init, as recorded
+    from it in golden_direct.npz (gen_golden.py --direct); where the reference
+    is compiled here, its own tables are read too and must be the recorded ones."""
     log, exp, skew, _ = const_tables
-    ref = ol.reference()
-    if ref is None:
-        pytest.skip("compiled reference (oracle/_ref) not built")
-    # the reference builds its tables in leo_init (CpuCodec called it)
-    ref_log = _ref_static_table("_ZN7leopard3ff8L6LogLUTE", 256, ctypes.c_uint8).astype(np.int64)
-    ref_exp = _ref_static_table("_ZN7leopard3ff8L6ExpLUTE", 256, ctypes.c_uint8).astype(np.int64)
-    ref_skew = _ref_static_table("_ZN7leopard3ff8L7FFTSkewE", 255, ctypes.c_uint8).astype(np.int64)
+    with np.load(os.path.join(HERE, "golden", "golden_direct.npz")) as z:
+        ref_log, ref_exp, ref_skew = (z[n].astype(np.int64) for n in ("ff8_log", "ff8_exp", "ff8_skew"))
+    for name, recorded in (("ff8_log", ref_log), ("ff8_exp", ref_exp), ("ff8_skew", ref_skew)):
+        here = ol.reference_static_table(*ol.REF_FF8_TABLES[name], ctypes.c_uint8)
+        if here is not None:
+            assert np.array_equal(here.astype(np.int64), recorded), name
     assert np.array_equal(log, ref_log)
     assert np.array_equal(exp, ref_exp)  # incl. the wrap ExpLUT[kModulus] = ExpLUT[0] (LeopardFF8.cpp:191)
     assert np.array_equal(skew, np.where(ref_skew == 255, 0, exp[np.minimum(ref_skew, 255)]))

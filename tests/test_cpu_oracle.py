@@ -52,22 +52,27 @@ def test_oracle_roundtrip_benchmark_pattern():
         assert np.array_equal(got[i], data[i])
 
 
-@pytest.mark.skipif(ol.reference() is None, reason="reference not compiled here (make -C oracle ref)")
-@pytest.mark.parametrize("k,r,b", [(2, 2, 64), (77, 31, 128), (128, 128, 64), (200, 56, 64), (129, 100, 64),
-                                   (1000, 500, 64), (3000, 1, 64), (1, 1, 64)])
+@pytest.mark.parametrize("k,r,b", ol.DIRECT_SHAPES)
 def test_oracle_vs_compiled_reference(k, r, b):
-    rng = np.random.default_rng(k * 1000 + r)
-    data = rng.integers(0, 256, (k, b), dtype=np.uint8)
-    ref = ol.reference()
-    assert np.array_equal(ol.oracle().encode(data, r), ref.encode(data, r))
-    junk = rng.integers(0, 256, (r, b), dtype=np.uint8)
-    loss = min(r, k)
-    lo = sorted(rng.choice(k, loss, replace=False).tolist())
-    lr = sorted(rng.choice(r, r - loss, replace=False).tolist())
+    """The oracle against the compiled reference's outputs on the same inputs:
+    as recorded from it in golden_direct.npz (gen_golden.py --direct), and
+    against the library itself where it is compiled here."""
+    data, junk, lo, lr = ol.direct_case(k, r, b)
+    tag = f"{k}_{r}_{b}"
+    with np.load(os.path.join(GOLDEN, "golden_direct.npz")) as z:
+        ref_enc, ref_dec, ref_lo = z["enc_" + tag], z["dec_" + tag], z["lo_" + tag].tolist()
+    assert lo == ref_lo, "the inputs differ from the recorded ones (numpy's Generator stream): regenerate"
+    enc = ol.oracle().encode(data, r)
+    assert np.array_equal(enc, ref_enc)
     a = ol.oracle().decode(data, junk, lo, lr)
-    e = ref.decode(data, junk, lo, lr)
-    for i in lo:
-        assert np.array_equal(a[i], e[i])
+    for j, i in enumerate(lo):
+        assert np.array_equal(a[i], ref_dec[j])
+    ref = ol.reference()
+    if ref is not None:
+        assert np.array_equal(enc, ref.encode(data, r))
+        e = ref.decode(data, junk, lo, lr)
+        for i in lo:
+            assert np.array_equal(a[i], e[i])
 
 
 def test_pcg_matches_reference_generator():

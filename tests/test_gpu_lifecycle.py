@@ -409,15 +409,15 @@ def test_tuning_switches_at_non_default_values():
 
 @pytest.mark.gpu
 def test_bench_line_batch_timing_small():
-    """bench.py end to end at a small size (4 objects in launches of 2, 2 streams):
-    one JSON line whose roofline launch time comes from the events inside the
-    timed region (GPU time per launch <= a launch's own span; achieved =
-    algorithmic bytes / launch time)."""
+    """bench.py --full end to end at a small size (4 objects in launches of 2, 2
+    streams): one JSON line whose roofline launch time comes from the events
+    inside the timed region (GPU time per launch <= a launch's own span;
+    achieved = algorithmic bytes / launch time)."""
     import json
     import subprocess
     import sys
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    p = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--steps", "3", "--warmup", "1",
+    p = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--full", "--steps", "3", "--warmup", "1",
                         "--objects", "4", "--launch-objects", "2", "--sets", "8", "--no-host", "--no-cpu-baseline",
                         "--no-sharded", "--no-secondary"], capture_output=True, text=True, timeout=110)
     assert p.returncode == 0, p.stderr[-2000:]
@@ -428,3 +428,42 @@ def test_bench_line_batch_timing_small():
     assert 0 < r["launch_us"] <= span * 1.05
     assert abs(r["achieved"] - r["algorithmic_bytes_per_launch"] / r["launch_us"] / 1e3) <= 0.01 * r["achieved"] + 0.01
     assert r["frac"] < 1.0
+
+
+@pytest.mark.gpu
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain bench.py run at a small size (4 objects in launches of 2): the
+    headline line alone, value = input bytes of the timed steps over their time,
+    ms_per_step that time per step; --dump-outputs writes what the last timed
+    step computed (buffer sets 0..3 here): the decoded originals are the inputs,
+    the recovery pieces the oracle's."""
+    import json
+    import subprocess
+    import sys
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    import bench  # the repository root is on sys.path (conftest.py)
+    p = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--objects", "4", "--launch-objects", "2", "--sets", "8", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=110)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, p.stdout
+    d = json.loads(lines[0])
+    assert d["full"] is False and d["steps"] == 3 and d["warmup"] == 1
+    assert not {"roofline", "modes", "cpu_baseline", "sharded_object", "host_e2e", "secondary", "breadth"} & set(d)
+    assert d["unit"] == "GB/s" and d["higher_is_better"] is True and d["dtype"] == "u8"
+    k = r = 128
+    b = 65536
+    assert d["ms_per_step"] > 0
+    assert d["value"] == pytest.approx(4 * k * b / (d["ms_per_step"] * 1e-3) / 1e9, rel=0.01)
+    files = {f: np.load(tmp_path / f) for f in d["dump_outputs"]["files"]}
+    assert sorted(files) == sorted(os.listdir(tmp_path))
+    assert sum(a.nbytes for a in files.values()) <= 64_000_000
+    pos = bench.dump_positions(k * b, 4)
+    for j in range(4):
+        orig = ol.hash_bytes(7 + j, k, b)
+        assert np.array_equal(files["decoded.npy"][j], orig.reshape(-1)[pos].astype(np.float32))
+        assert np.array_equal(files["decoded_sums.npy"][j], orig.sum(axis=1, dtype=np.int64).astype(np.float64))
+    rec = ol.oracle().encode(ol.hash_bytes(7, k, b), r)
+    assert np.array_equal(files["recovery.npy"][0], rec.reshape(-1)[pos].astype(np.float32))
+    assert np.array_equal(files["recovery_sums.npy"][0], rec.sum(axis=1, dtype=np.int64).astype(np.float64))

@@ -8,8 +8,8 @@ import subprocess
 import sys
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-args = sys.argv[1:] or ["--steps", "100", "--warmup", "10", "--no-host", "--no-cpu-baseline", "--no-sharded",
-                        "--no-secondary"]
+args = ["--full"] + (sys.argv[1:] or ["--steps", "100", "--warmup", "10", "--no-host", "--no-cpu-baseline",
+                                       "--no-sharded", "--no-secondary"])  # --full: the roofline legs
 p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py")] + args, capture_output=True, text=True)
 if p.returncode != 0:
     sys.stderr.write(p.stderr[-3000:])

@@ -1,6 +1,7 @@
 #!/bin/bash
 # GPU-box: default bench line, then the same command under rocprofv3 kernel trace.
 set -o pipefail
+BENCH_ARGS="--full ${BENCH_ARGS:-}"  # every leg of the line, not the headline run alone
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
 timeout -k 10 600 python bench.py ${BENCH_ARGS:-} > gpurun_out/bench.json 2> gpurun_out/bench.err || { tail -30 gpurun_out/bench.err; exit 1; }

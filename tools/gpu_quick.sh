@@ -1,6 +1,7 @@
 #!/bin/bash
 # GPU box: selected GPU tests (PYTEST_K, all when empty), then bbench / kbench / bench as asked.
 set -o pipefail
+BENCH_ARGS="--full ${BENCH_ARGS:-}"  # every leg of the line, not the headline run alone
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
 timeout -k 10 ${PYTEST_TIMEOUT:-400} python3 -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread ${PYTEST_K:+-k "$PYTEST_K"} > gpurun_out/pytest_q.log 2>&1; rc=$?

@@ -3,6 +3,7 @@
 # then the FETCH_SIZE / WRITE_SIZE passes for roofline.traffic.  Each step under its
 # own time limit; stop at the first failure.
 set -o pipefail
+BENCH_ARGS="--full ${BENCH_ARGS:-}"  # every leg of the line, not the headline run alone
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
 mkdir -p gpurun_out
