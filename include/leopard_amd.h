@@ -80,6 +80,54 @@ LEO_EXPORT LeopardResult leo_amd_decode_batch(
     unsigned work_count, const void* const* const* original_data, const void* const* const* recovery_data,
     void** const* work_data);
 
+/* In-place recovery update from original-piece deltas (the parity-delta
+ * update of a partial-stripe write).  The code is linear in every byte column:
+ * encode(D ^ delta) == encode(D) ^ encode(delta), so when a few originals
+ * change, the recovery pieces change by a sum over the changed pieces only,
+ * and the unchanged originals are not needed.
+ *
+ * recovery_data[j] ^= XOR_t G[j][changed_index[t]] * delta_data[t], j < recovery_count, in place.
+ * If recovery_data held leo_encode's output for originals D, it afterwards holds, bit for bit,
+ * leo_encode's output for D with D[changed_index[t]] ^= delta_data[t].
+ *
+ * delta_data[t] is new piece XOR old piece of original changed_index[t]
+ * (buffer_bytes bytes, read only).  At most LEO_AMD_UPDATE_MAX_CHANGED pieces
+ * a call; a caller with more calls again or re-encodes.  All delta and
+ * recovery pieces are of one kind: device memory (updated on the calling
+ * thread's stream, honouring leo_amd_set_stream / set_async / set_device) or
+ * host memory (registered ranges in place, pageable memory staged; the call
+ * returns when the results are in host memory).  Deltas must not overlap
+ * recovery pieces (not checked).
+ *
+ * Results, in this order, all decided before any GPU work:
+ * Leopard_InvalidSize (buffer_bytes 0 or not a multiple of 64; slice form:
+ * the slice checks of leo_amd_encode_slice); Leopard_InvalidCounts
+ * (recovery_count 0 or > original_count, changed_count >
+ * LEO_AMD_UPDATE_MAX_CHANGED); changed_count == 0 returns Leopard_Success and
+ * touches nothing; Leopard_InvalidInput (a NULL array, a NULL delta_data[t] or
+ * recovery_data[j], an index >= original_count, a repeated index;
+ * leo_amd_last_error() names the position); Leopard_CallInitialize;
+ * Leopard_TooMuchData (codeword length above 65536).
+ *
+ * The coefficients G[j][i] come from the library's own encoder and are cached
+ * per device by (original_count, recovery_count, index), up to
+ * LEO_AMD_UPDATE_CACHE_KB KiB (environment, read once; default 65536; 0 = no
+ * caching).  Past that bound a call still succeeds: it builds the columns it
+ * needs in scratch of its own. */
+#define LEO_AMD_UPDATE_MAX_CHANGED 32
+
+LEO_EXPORT LeopardResult leo_amd_update(
+    uint64_t buffer_bytes, unsigned original_count, unsigned recovery_count,
+    unsigned changed_count, const unsigned* changed_index,
+    const void* const* delta_data, void** recovery_data);
+
+/* The same over bytes [byte_offset, byte_offset + slice_bytes) of each piece. */
+LEO_EXPORT LeopardResult leo_amd_update_slice(
+    uint64_t buffer_bytes, uint64_t byte_offset, uint64_t slice_bytes,
+    unsigned original_count, unsigned recovery_count,
+    unsigned changed_count, const unsigned* changed_index,
+    const void* const* delta_data, void** recovery_data);
+
 /* Caller-registered host memory: pins [ptr, ptr + bytes) and maps it for
  * every device.  leo_encode / leo_decode calls whose host pieces all lie in
  * registered ranges run the kernels on them in place (reads and writes over

@@ -34,7 +34,7 @@ LEO_VERSION = 2
 __all__ = [
     "LEO_VERSION", "LeopardResult", "leo_init", "leo_result_string", "leo_encode_work_count", "leo_encode",
     "leo_decode_work_count", "leo_decode", "leo_amd_encode_slice", "leo_amd_decode_slice", "leo_amd_encode_batch",
-    "leo_amd_decode_batch", "register_host", "unregister_host", "set_fanout", "set_stream", "release_stream",
+    "leo_amd_decode_batch", "leo_amd_update", "leo_amd_update_slice", "UPDATE_MAX_CHANGED", "update", "register_host", "unregister_host", "set_fanout", "set_stream", "release_stream",
     "set_async", "set_device", "device_count", "table", "last_error", "encode", "decode", "LIB_PATH", "lib",
 ]
 
@@ -72,6 +72,8 @@ def _load():
         "leo_amd_decode_slice": (i, [u64, u64, u64, u, u, u, pp, pp, pp]),
         "leo_amd_encode_batch": (i, [u, u64, u, u, u, ctypes.POINTER(pp), ctypes.POINTER(pp)]),
         "leo_amd_decode_batch": (i, [u, u64, u, u, u, ctypes.POINTER(pp), ctypes.POINTER(pp), ctypes.POINTER(pp)]),
+        "leo_amd_update": (i, [u64, u, u, u, ctypes.POINTER(u), pp, pp]),
+        "leo_amd_update_slice": (i, [u64, u64, u64, u, u, u, ctypes.POINTER(u), pp, pp]),
         "leo_amd_register_host": (i, [vp, u64]),
         "leo_amd_unregister_host": (i, [vp]),
         "leo_amd_set_stream": (None, [vp]),
@@ -180,6 +182,32 @@ def leo_amd_decode_batch(buffer_bytes, original_count, recovery_count, work_coun
                                                   _ptr_arrays(work_data)))
 
 
+UPDATE_MAX_CHANGED = 32  # LEO_AMD_UPDATE_MAX_CHANGED
+
+
+def _uints(seq):
+    return (ctypes.c_uint * max(len(seq), 1))(*[int(v) for v in seq])
+
+
+def leo_amd_update(buffer_bytes, original_count, recovery_count, changed_count, changed_index, delta_data,
+                   recovery_data) -> LeopardResult:
+    """recovery_data[j] ^= XOR_t G[j][changed_index[t]] * delta_data[t], in place (include/leopard_amd.h).
+    Arrays are sequences (of indices / addresses) or None for a NULL array."""
+    ci = None if changed_index is None else _uints(changed_index)
+    dd = None if delta_data is None else _ptrs(delta_data)
+    rd = None if recovery_data is None else _ptrs(recovery_data)
+    return LeopardResult(lib.leo_amd_update(buffer_bytes, original_count, recovery_count, changed_count, ci, dd, rd))
+
+
+def leo_amd_update_slice(buffer_bytes, byte_offset, slice_bytes, original_count, recovery_count, changed_count,
+                         changed_index, delta_data, recovery_data) -> LeopardResult:
+    ci = None if changed_index is None else _uints(changed_index)
+    dd = None if delta_data is None else _ptrs(delta_data)
+    rd = None if recovery_data is None else _ptrs(recovery_data)
+    return LeopardResult(lib.leo_amd_update_slice(buffer_bytes, byte_offset, slice_bytes, original_count,
+                                                  recovery_count, changed_count, ci, dd, rd))
+
+
 def register_host(ptr: int, nbytes: int) -> LeopardResult:
     """Pin + map a caller-owned host range (include/leopard_amd.h)."""
     return LeopardResult(lib.leo_amd_register_host(ctypes.c_void_p(ptr), nbytes))
@@ -268,3 +296,20 @@ def decode(original, recovery, lost_originals, lost_recovery=(), work=None):
                      [work[i].data_ptr() for i in range(wc)])
     _check(res, "leo_decode")
     return {i: work[i] for i in sorted(lo)}
+
+
+def update(recovery, original_count: int, indices, deltas):
+    """Parity-delta update: recovery [R, B] uint8 (device or host, rows contiguous)
+    becomes the encoding of the originals with original indices[t] ^= deltas[t];
+    deltas [C, B] of the same kind.  In place; returns recovery."""
+    r, nbytes = recovery.shape
+    indices = [int(i) for i in indices]
+    if len(indices) != deltas.shape[0] or deltas.shape[1] != nbytes:
+        raise ValueError(f"deltas {tuple(deltas.shape)} do not match {len(indices)} indices of {nbytes} bytes")
+    if recovery.stride(1) != 1 or deltas.stride(1) != 1:
+        raise ValueError("pieces must be contiguous rows")
+    res = leo_amd_update(nbytes, original_count, r, len(indices), indices,
+                         [deltas[t].data_ptr() for t in range(len(indices))],
+                         [recovery[j].data_ptr() for j in range(r)])
+    _check(res, "leo_amd_update")
+    return recovery

@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <condition_variable>
 #include <cstdio>
@@ -2268,6 +2269,316 @@ LeopardResult decode_checked(uint64_t bytes, uint64_t off, unsigned K, unsigned 
     return decode_any(bytes, off, K, R, orig, rec, work);
 }
 
+// -------------------------------------------------------------- update ----
+// leo_amd_update: recovery_j ^= XOR_t G[j][i_t] * delta_t (rs_update.hip), G
+// the encoder's coefficient matrix.  A column of G (one changed original: R
+// coefficients as multiply tables, in output order) comes from the encoder's
+// own kernels: one encode of K pieces of 64 bytes in which changed piece u is
+// the unit piece with byte u = 1 and every other piece the zero page, so byte
+// u of output j is G[j][i_u] (GF(2^16): low byte at u, high byte at 32 + u,
+// the two halves of the 64-byte block).  k_upd_tabs turns the values into
+// tables (GF(2^8): the value-indexed tables; GF(2^16): the log-indexed tables
+// through a value -> log table uploaded once per device).
+//
+// Columns are cached per device by (K, R, index) with MatEntry's discipline:
+// written once, on the stream of the call that first needs them, `ready`
+// recorded after the writes, never rewritten or freed; a call on another
+// stream waits for `ready` on the device.  A call generates the columns it
+// does not find in one encoder run.  At most LEO_AMD_UPDATE_CACHE_KB KiB of
+// columns a device (read once; default kUpdCacheDefaultKb; 0: no caching); a
+// column that does not fit is built in per-call scratch, freed in stream
+// order after the call's kernels.  No eviction.
+struct UpdReady {
+    hipEvent_t ev = nullptr;
+    std::atomic<bool> done{false};
+};
+struct UpdColumn {
+    uint32_t* tabs = nullptr;
+    std::shared_ptr<UpdReady> ready;  // one event per generation run
+};
+struct UpdCache {
+    std::mutex mu;
+    std::map<std::array<unsigned, 3>, UpdColumn> cols;
+    size_t bytes = 0;
+    uint16_t* vlog16 = nullptr;  // GF(2^16) value -> log
+};
+std::vector<std::unique_ptr<UpdCache>> g_upd;  // per device
+static_assert(kUpdMaxChanged == LEO_AMD_UPDATE_MAX_CHANGED, "the header's cap is the kernels'");
+constexpr long kUpdCacheDefaultKb = 64 << 10;
+size_t upd_cache_limit() {
+    static const size_t v = [] {
+        const char* e = std::getenv("LEO_AMD_UPDATE_CACHE_KB");
+        const long kb = e ? std::atol(e) : kUpdCacheDefaultKb;
+        return size_t(std::max(0L, kb)) << 10;
+    }();
+    return v;
+}
+
+// GF(2^16) columns as log values instead of copied tables (A/B):
+// LEO_AMD_UPD_LOGS=1 in experiment builds; read once.
+bool upd_logs() {
+#if LAMD_EXPERIMENT_ENV
+    static const bool v = [] { const char* e = std::getenv("LEO_AMD_UPD_LOGS"); return e && e[0] == '1'; }();
+    return v;
+#else
+    return false;
+#endif
+}
+
+// The columns of changed pieces idx[0, C) for this call: cached ones, and the
+// rest generated now.  Columns in per-call scratch are appended to `scratch`
+// (the caller frees them on the stream after its kernels).
+LeopardResult update_columns(Call& c, bool ff16, unsigned K, unsigned R, unsigned C, const unsigned* idx,
+                             const uint32_t** cols, std::vector<void*>& scratch) {
+    UpdCache& uc = *g_upd[c.dev];
+    std::lock_guard<std::mutex> lk(uc.mu);  // generation is a few launches, once per column
+    unsigned miss[kUpdMaxChanged], nmiss = 0;
+    for (unsigned t = 0; t < C; ++t) {
+        const auto it = uc.cols.find({K, R, idx[t]});
+        if (it == uc.cols.end()) {
+            miss[nmiss++] = t;
+            continue;
+        }
+        UpdReady& rd = *it->second.ready;
+        if (!rd.done.load(std::memory_order_acquire)) {
+            if (hipEventQuery(rd.ev) == hipSuccess) rd.done.store(true, std::memory_order_release);
+            else HIP_OK(hipStreamWaitEvent(c.s, rd.ev, 0), "wait for update column");  // built on another stream
+        }
+        cols[t] = it->second.tabs;
+    }
+    if (nmiss == 0) return Leopard_Success;
+    if (ff16 && !uc.vlog16) {
+        const std::vector<uint16_t>& lg = field16().log_of;
+        HIP_OK(hipMalloc(reinterpret_cast<void**>(&uc.vlog16), lg.size() * sizeof(uint16_t)), "value -> log table");
+        HIP_OK(hipMemcpy(uc.vlog16, lg.data(), lg.size() * sizeof(uint16_t), hipMemcpyHostToDevice),
+               "value -> log table");
+    }
+    // one encoder run: unit pieces for the missing columns, the zero page for the rest
+    constexpr unsigned kPitch = 64;
+    uint8_t* gen = nullptr;
+    HIP_OK(pool_alloc(reinterpret_cast<void**>(&gen), size_t(nmiss + R) * kPitch, c.dev, c.s), "allocate unit pieces");
+    c.ws->touched = true;
+    uint8_t* units = gen;
+    uint8_t* rows = gen + size_t(nmiss) * kPitch;
+    const size_t tab_dw = ff16 ? kTab16Dwords : kTab8Dwords;
+    const bool logs = ff16 && upd_logs();
+    const size_t col_bytes = logs ? size_t(R) * 4 : size_t(R) * tab_dw * 4;
+    UpdTabArgs ta;
+    std::memset(&ta, 0, sizeof(ta));
+    bool cached[kUpdMaxChanged] = {};
+    bool any_cached = false;
+    auto fail = [&](LeopardResult r) {  // nothing queued reads what is freed here
+        (void)hipFreeAsync(gen, c.s);
+        for (unsigned u = 0; u < nmiss; ++u)
+            if (ta.dst[u]) (void)hipFreeAsync(ta.dst[u], c.s);
+        return r;
+    };
+    hipError_t e = launch_ff8_unit(units, nmiss, kPitch, c.s);
+    if (e != hipSuccess) {
+        set_error("unit pieces", e);
+        return fail(Leopard_Platform);
+    }
+    {
+        std::vector<const void*> o(K, c.t->zeros);
+        std::vector<void*> w(R);
+        for (unsigned u = 0; u < nmiss; ++u) o[idx[miss[u]]] = units + size_t(u) * kPitch;
+        for (unsigned j = 0; j < R; ++j) w[j] = rows + size_t(j) * kPitch;
+        tls_mat_gen = true;  // the transform kernels, never the matrix path
+        const LeopardResult r = encode_device(c, kPitch, 0, K, R, o.data(), w.data());
+        tls_mat_gen = false;
+        if (r != Leopard_Success) return fail(r);
+    }
+    size_t add = 0;
+    for (unsigned u = 0; u < nmiss; ++u) {
+        cached[u] = uc.bytes + add + col_bytes <= upd_cache_limit();
+        e = pool_alloc(reinterpret_cast<void**>(&ta.dst[u]), col_bytes, c.dev, c.s);
+        if (e != hipSuccess) {
+            set_error("allocate update column", e);
+            return fail(Leopard_Platform);
+        }
+        if (cached[u]) add += col_bytes, any_cached = true;
+        ta.pos[u] = uint8_t(u);
+    }
+    ta.rows = rows;
+    ta.tabs = ff16 ? c.t->tab16 : c.t->vtab8;
+    ta.vlog = uc.vlog16;
+    ta.R = R;
+    ta.n = nmiss;
+    ta.logs = logs;
+    e = launch_update_tabs(ff16, ta, c.s);
+    if (e != hipSuccess) {
+        set_error("update column tables", e);
+        return fail(Leopard_Platform);
+    }
+    std::shared_ptr<UpdReady> rd;
+    if (any_cached) {
+        rd = std::make_shared<UpdReady>();
+        e = hipEventCreateWithFlags(&rd->ev, kOrderEvent);
+        if (e == hipSuccess) e = hipEventRecord(rd->ev, c.s);
+        if (e != hipSuccess) {  // no event to order other streams by: keep nothing
+            set_error("record update columns", e);
+            return fail(Leopard_Platform);
+        }
+    }
+    for (unsigned u = 0; u < nmiss; ++u) {
+        cols[miss[u]] = ta.dst[u];
+        if (cached[u]) uc.cols[{K, R, idx[miss[u]]}] = UpdColumn{ta.dst[u], rd};
+        else scratch.push_back(ta.dst[u]);
+    }
+    uc.bytes += add;
+    HIP_OK(hipFreeAsync(gen, c.s), "free unit pieces");
+    return Leopard_Success;
+}
+
+// out_j = base_j ^ XOR_t G[j][idx[t]] * delta_t over columns [off, off + bytes)
+// of device-visible pieces (base == out: in place).  R == 1 (and with it
+// K == 1) is the reference encoder's XOR / copy (leopard.cpp:144-160): every
+// coefficient is 1, in either field.
+LeopardResult update_device(Call& c, uint64_t bytes, uint64_t off, unsigned K, unsigned R, unsigned C,
+                            const unsigned* idx, const void* const* delta, const void* const* base, void* const* out) {
+    const bool edge = R == 1;
+    const bool ff16 = !edge && next_pow2(next_pow2(R) + K) > 256;
+    const uint32_t* cols[kUpdMaxChanged] = {};
+    std::vector<void*> scratch;
+    if (edge) {
+        for (unsigned t = 0; t < C; ++t) cols[t] = c.t->vtab8 + kTab8Dwords;  // the table of the value 1
+    } else {
+        const LeopardResult r = update_columns(c, ff16, K, R, C, idx, cols, scratch);
+        if (r != Leopard_Success) return r;
+    }
+    auto release = [&](LeopardResult r) {
+        for (void* p : scratch) (void)hipFreeAsync(p, c.s);
+        return r;
+    };
+    UpdArgs proto;
+    std::memset(&proto, 0, sizeof(proto));
+    MapBuilder mb;
+    bool in_place = true;
+    for (unsigned j = 0; j < R && in_place; ++j) in_place = base[j] == out[j];
+    mb.build(proto.out, const_cast<const void* const*>(out), R, 0);
+    if (!in_place) mb.build(proto.base, base, R, 0);
+    LeopardResult r = c.ws->reserve_device((mb.bytes() + 255) / 256 * 256);
+    if (r != Leopard_Success) return release(r);
+    r = mb.flush(*c.ws, reinterpret_cast<uint64_t*>(c.ws->dbuf), c.s);
+    if (r != Leopard_Success) return release(r);
+    if (in_place) proto.base = proto.out;
+    proto.R = R;
+    proto.tab16 = c.t->tab16;
+    proto.col_logs = ff16 && upd_logs();
+    // launches of at most kUpdMaxLaunchBytes columns (32-bit byte offsets in
+    // the kernel) and kUpdChunk deltas; chunks after the first accumulate
+    // into what the first one wrote
+    for (uint64_t pos = 0; pos < bytes; pos += kUpdMaxLaunchBytes) {
+        const uint64_t len = std::min(kUpdMaxLaunchBytes, bytes - pos);
+        for (unsigned t0 = 0; t0 < C; t0 += kUpdChunk) {
+            const unsigned n = std::min(kUpdChunk, C - t0);
+            UpdArgs a = proto;
+            if (t0 > 0) a.base = a.out;
+            a.base.off = a.out.off = off + pos;
+            for (unsigned u = 0; u < n; ++u) {
+                a.delta[u] = uint64_t(reinterpret_cast<uintptr_t>(delta[t0 + u])) + off + pos;
+                a.col[u] = cols[t0 + u];
+            }
+            a.nbytes = uint32_t(len);
+            const hipError_t e = launch_update(ff16, a, n, c.t->cus, c.s);
+            if (e != hipSuccess) {
+                set_error("update kernel", e);
+                return release(Leopard_Platform);
+            }
+        }
+    }
+    return release(Leopard_Success);
+}
+
+// Validation of leo_amd_update / leo_amd_update_slice, everything decided
+// before any GPU call, in check_encode's order.  *nothing: changed_count == 0.
+LeopardResult check_update(uint64_t bytes, unsigned K, unsigned R, unsigned C, const unsigned* idx,
+                           const void* const* delta, void* const* rec, bool* nothing) {
+    *nothing = false;
+    if (bytes == 0 || bytes % 64 != 0) return Leopard_InvalidSize;
+    if (R == 0 || R > K || C > kUpdMaxChanged) return Leopard_InvalidCounts;
+    if (C == 0) {
+        *nothing = true;
+        return Leopard_Success;
+    }
+    char buf[128];
+    auto invalid = [&]() {
+        tls.last_error = buf;
+        return Leopard_InvalidInput;
+    };
+    if (!idx || !delta || !rec) {
+        std::snprintf(buf, sizeof(buf), "%s is NULL with changed_count %u",
+                      !idx ? "changed_index" : !delta ? "delta_data" : "recovery_data", C);
+        return invalid();
+    }
+    for (unsigned t = 0; t < C; ++t)
+        if (!delta[t]) {
+            std::snprintf(buf, sizeof(buf), "delta_data[%u] is NULL", t);
+            return invalid();
+        }
+    for (unsigned j = 0; j < R; ++j)
+        if (!rec[j]) {
+            std::snprintf(buf, sizeof(buf), "recovery_data[%u] is NULL", j);
+            return invalid();
+        }
+    for (unsigned t = 0; t < C; ++t) {
+        if (idx[t] >= K) {
+            std::snprintf(buf, sizeof(buf), "changed_index[%u] = %u is not below original_count %u", t, idx[t], K);
+            return invalid();
+        }
+        for (unsigned u = 0; u < t; ++u)
+            if (idx[u] == idx[t]) {
+                std::snprintf(buf, sizeof(buf), "changed_index[%u] repeats changed_index[%u] = %u", t, u, idx[t]);
+                return invalid();
+            }
+    }
+    if (!g_initialized) return Leopard_CallInitialize;
+    if (K == 1 || R == 1) return Leopard_Success;
+    if (next_pow2(next_pow2(R) + K) > 65536) return Leopard_TooMuchData;
+    return Leopard_Success;
+}
+
+LeopardResult update_any(uint64_t bytes, uint64_t off, unsigned K, unsigned R, unsigned C, const unsigned* idx,
+                         const void* const* delta, void** rec) {
+    MemKind kind;
+    const int dev = pick_device(rec[0], &kind);
+    DeviceGuard guard(dev);
+    Call c;
+    LeopardResult r = begin_call(dev, c);
+    if (r != Leopard_Success) return r;
+    if (kind == MemKind::Device) {
+        r = update_device(c, bytes, off, K, R, C, idx, delta, const_cast<const void* const*>(rec), rec);
+        if (r != Leopard_Success) return r;
+        return finish(c, false);
+    }
+    {  // caller-registered host memory: the kernels run on it in place
+        std::vector<void*> dd, dr;
+        if (map_registered(delta, C, off, bytes, dd) && map_registered(const_cast<const void* const*>(rec), R, off, bytes, dr)) {
+            r = update_device(c, bytes, off, K, R, C, idx, const_cast<const void* const*>(dd.data()),
+                              const_cast<const void* const*>(dr.data()), dr.data());
+            if (r != Leopard_Success) return r;
+            return finish(c, true);
+        }
+    }
+    // pageable host memory, staged as dense rows: inputs = the C deltas, then
+    // the R old recovery pieces; outputs = the R new recovery pieces
+    const SliceFn slice_fn = [&](Call& cs, uint64_t len, uint8_t* din, uint8_t* dout, uint64_t stride) {
+        std::vector<const void*> dd(C), db(R);
+        std::vector<void*> dw(R);
+        for (unsigned t = 0; t < C; ++t) dd[t] = din + t * stride;
+        for (unsigned j = 0; j < R; ++j) db[j] = din + (uint64_t(C) + j) * stride;
+        for (unsigned j = 0; j < R; ++j) dw[j] = dout + j * stride;
+        return update_device(cs, len, 0, K, R, C, idx, dd.data(), db.data(), dw.data());
+    };
+    std::vector<const uint8_t*> hin(C + R);
+    std::vector<uint8_t*> hout(R);
+    for (unsigned t = 0; t < C; ++t) hin[t] = static_cast<const uint8_t*>(delta[t]) + off;
+    for (unsigned j = 0; j < R; ++j) hin[C + j] = hout[j] = static_cast<uint8_t*>(rec[j]) + off;
+    r = run_host_pipeline(c, bytes, hin, hout, slice_fn);
+    if (r != Leopard_Success) return r;
+    return finish(c, true);
+}
+
 // ------------------------------------------------------------- batches ----
 
 // leo_amd_encode_batch / leo_amd_decode_batch: `count` independent objects of
@@ -2744,6 +3055,8 @@ LEO_EXPORT int leo_init_(int version) {
     g_dev.assign(count, DeviceTables{});
     g_mat.clear();
     for (int i = 0; i < count; ++i) g_mat.emplace_back(new MatCache);
+    g_upd.clear();
+    for (int i = 0; i < count; ++i) g_upd.emplace_back(new UpdCache);
     g_device_count = count;
     g_initialized = true;
     std::atexit([] { g_exiting.store(true); });  // after the runtime's own registration: runs before its teardown
@@ -2814,6 +3127,31 @@ LEO_EXPORT LeopardResult leo_amd_decode_slice(uint64_t buffer_bytes, uint64_t by
     if (r != Leopard_Success) return r;
     return decode_checked(slice_bytes, byte_offset, original_count, recovery_count, work_count, original_data,
                           recovery_data, work_data);
+}
+
+LEO_EXPORT LeopardResult leo_amd_update(uint64_t buffer_bytes, unsigned original_count, unsigned recovery_count,
+                                        unsigned changed_count, const unsigned* changed_index,
+                                        const void* const* delta_data, void** recovery_data) {
+    bool nothing = false;
+    LeopardResult r = check_update(buffer_bytes, original_count, recovery_count, changed_count, changed_index,
+                                   delta_data, recovery_data, &nothing);
+    if (r != Leopard_Success || nothing) return r;
+    return update_any(buffer_bytes, 0, original_count, recovery_count, changed_count, changed_index, delta_data,
+                      recovery_data);
+}
+
+LEO_EXPORT LeopardResult leo_amd_update_slice(uint64_t buffer_bytes, uint64_t byte_offset, uint64_t slice_bytes,
+                                              unsigned original_count, unsigned recovery_count,
+                                              unsigned changed_count, const unsigned* changed_index,
+                                              const void* const* delta_data, void** recovery_data) {
+    if (slice_bytes == 0 || slice_bytes % 64 || byte_offset % 64 || byte_offset + slice_bytes > buffer_bytes)
+        return Leopard_InvalidSize;
+    bool nothing = false;
+    LeopardResult r = check_update(buffer_bytes, original_count, recovery_count, changed_count, changed_index,
+                                   delta_data, recovery_data, &nothing);
+    if (r != Leopard_Success || nothing) return r;
+    return update_any(slice_bytes, byte_offset, original_count, recovery_count, changed_count, changed_index,
+                      delta_data, recovery_data);
 }
 
 LEO_EXPORT LeopardResult leo_amd_encode_batch(unsigned object_count, uint64_t buffer_bytes, unsigned original_count,

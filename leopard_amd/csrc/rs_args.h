@@ -233,6 +233,43 @@ hipError_t launch_ff8_unit(uint8_t* out, unsigned n, unsigned pitch, hipStream_t
 hipError_t launch_ff8_mat_tabs(const uint8_t* rows, unsigned pitch, unsigned L, unsigned N, const uint32_t* vtab,
                                uint32_t* tabs, hipStream_t s);
 
+// In-place recovery update (rs_update.hip): out_j = base_j ^ XOR_t g[j][t] *
+// delta_t for j < R and at most kUpdChunk deltas a launch (a call with more
+// runs further launches with base = out).  Column t holds the multiply tables
+// of g[.][t], one per output in output order (FF8: kTab8Dwords each, FF16:
+// kTab16Dwords), so a cached column serves every call that changes its piece.
+constexpr unsigned kUpdChunk = 8;
+constexpr unsigned kUpdMaxChanged = 32;  // LEO_AMD_UPDATE_MAX_CHANGED
+constexpr uint64_t kUpdMaxLaunchBytes = 1ull << 30;  // per piece and launch: byte offsets stay below 2^31
+struct UpdArgs {
+    uint64_t delta[kUpdChunk];       // delta pieces (column base applied)
+    const uint32_t* col[kUpdChunk];  // their columns of tables
+    PieceMap base, out;              // recovery pieces read / written (base == out: in place)
+    unsigned R;
+    unsigned G;        // outputs per workgroup row (set by the launcher)
+    uint32_t ngroups;  // lane groups per piece (set by the launcher)
+    uint32_t nbytes;   // bytes per piece in this launch (a multiple of 64, <= kUpdMaxLaunchBytes)
+    // GF(2^16) columns as log values (experiment builds): col[t][j] indexes tab16
+    const uint32_t* tab16;
+    uint32_t col_logs;
+};
+// deltas: how many of the kUpdChunk slots are in use (1..kUpdChunk)
+hipError_t launch_update(bool ff16, const UpdArgs& a, unsigned deltas, unsigned cus, hipStream_t s);
+// Columns from coefficient values: rows = the encoder's R output pieces of 64
+// bytes for unit inputs; column u's coefficient for output j is byte pos[u] of
+// row j (FF16: high byte at 32 + pos[u]).  FF8: tabs = value-indexed tables;
+// FF16: tabs = log-indexed tables (entry 65536 all zero), vlog = value -> log.
+struct UpdTabArgs {
+    uint32_t* dst[kUpdMaxChanged];
+    uint8_t pos[kUpdMaxChanged];
+    const uint8_t* rows;
+    const uint32_t* tabs;
+    const uint16_t* vlog;
+    unsigned R, n;
+    uint32_t logs;  // GF(2^16): write the table index (a dword per output) instead of the table
+};
+hipError_t launch_update_tabs(bool ff16, const UpdTabArgs& a, hipStream_t s);
+
 // Units per lane chosen for each kernel family (the host sizes grids with it).
 constexpr int kUnitsPerLane = 1;
 constexpr unsigned kUnitsPerTile = 64 * kUnitsPerLane;
