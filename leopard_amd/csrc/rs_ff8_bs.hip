@@ -34,9 +34,18 @@
 // The two layouts are exchanged through a wave-private LDS area (no barrier:
 // one wave's LDS operations execute in order).  No tables, no workgroup
 // barriers: waves are independent, several per SIMD.
+//
+// Workgroup-cooperative tile (WB wave bits, the product's batches run WB = 2):
+// the 1 << WB waves of a workgroup share one tile over a (256 << WB)-byte
+// strip.  A piece bit is then held by a register bit (4), a lane-group bit
+// (3 - WB) or the wave's index (WB).  A wave bit is wave-uniform: a code variant
+// per wave folds it into the constant A, so only 3 - WB lane bits are twisted
+// (WB = 2: one masked network in layer 0, none in layers 1-2).  The exchange
+// to layout top crosses the waves: one LDS area per workgroup, barriers.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstdlib>
 #include <type_traits>
 
 #include "gf8_const.h"
@@ -224,17 +233,23 @@ constexpr bool lay_ok(uint32_t L) {
 // with A_r = the skew of piece(r, 0) and H_j = the generator of bit gb[j]: the
 // "twist", selected per lane by the all-ones masks G[j] (checked here for every
 // layout the kernel uses).
-constexpr unsigned twist_at(int off, uint32_t L, unsigned r, unsigned l, unsigned j) {
-    const unsigned p = piece_of(L, r, 0);
+//
+// Wave bits (WB, the workgroup-cooperative tile below): the low WB bits of g
+// are not lane bits but the wave's index in its workgroup, wv.  They are
+// wave-uniform, so a code variant per wv folds them into A_r = the skew of
+// piece(r, wv) and only the bits j >= WB are twisted.
+constexpr unsigned twist_at(int off, uint32_t L, unsigned r, unsigned l, unsigned j, unsigned wv = 0) {
+    const unsigned p = piece_of(L, r, wv);
     return lay_gb(L, j) > l ? skew_at(off, p | (1u << lay_gb(L, j)), l) ^ skew_at(off, p, l) : 0u;
 }
-constexpr bool affine_ok(uint32_t L, unsigned l) {
+constexpr bool affine_ok(uint32_t L, unsigned l, unsigned WB = 0) {
     for (int off : {-1, 127})
         for (unsigned r = 0; r < 16; ++r)
             for (unsigned g = 0; g < 8; ++g) {
-                unsigned v = skew_at(off, piece_of(L, r, 0), l);
-                for (unsigned j = 0; j < 3; ++j)
-                    if ((g >> j) & 1u) v ^= twist_at(off, L, r, l, j);
+                const unsigned wv = g & ((1u << WB) - 1u);
+                unsigned v = skew_at(off, piece_of(L, r, wv), l);
+                for (unsigned j = WB; j < 3; ++j)
+                    if ((g >> j) & 1u) v ^= twist_at(off, L, r, l, j, wv);
                 if (v != skew_at(off, piece_of(L, r, g), l)) return false;
             }
     return true;
@@ -268,6 +283,12 @@ constexpr uint32_t kLayT = lay(3, 4, 5, 6, 0, 1, 2);
 #endif
 static_assert(lay_ok(kLay0) && lay_ok(kLay1) && lay_ok(kLay2) && lay_ok(kLayT), "layouts are bit permutations");
 static_assert(affine_ok(kLay0, 0) && affine_ok(kLay1, 1) && affine_ok(kLay2, 2), "skews are affine in the lane-group bits");
+// the workgroup-cooperative tiles: two waves (g bit 0 = piece bit 6 is the wave)
+// run the same layouts; four waves (g bits 0, 1 = piece bits 6, 5) have no lane
+// bit to trade for piece bit 1 and run layer 2 in kLay1
+static_assert(affine_ok(kLay0, 0, 1) && affine_ok(kLay1, 1, 1) && affine_ok(kLay2, 2, 1), "two-wave tile: every wave's variant");
+static_assert(affine_ok(kLay0, 0, 2) && affine_ok(kLay1, 1, 2) && affine_ok(kLay1, 2, 2), "four-wave tile: every wave's variant");
+static_assert(reg_bit_of(kLay1, 2) == 2 && reg_bit_of(kLay1, 3) == 3 && reg_bit_of(kLay2, 3) == 3, "register bit 3 = piece bit 3 in every low layout");
 
 // ----------------------------------------------------------- butterflies ---
 
@@ -276,7 +297,8 @@ using Reg = uint32_t[16][8];
 // Layer L in layout LAY: the pairs (r, r + 2^i) over the register bit i that
 // holds piece bit L, restricted to the half of register bit 3 = H (H < 0: all
 // 16 registers; the low layers never pair across it, it holds piece bit 3).
-template <bool kInverse, int kOff, int L, uint32_t LAY, int H = -1>
+// WB, WV: the low WB bits of g are wave bits and this is the code of wave WV.
+template <bool kInverse, int kOff, int L, uint32_t LAY, int H = -1, int WB = 0, unsigned WV = 0>
 LDEV void layer(Reg& x, const uint32_t (&G)[3]) {
     constexpr int ib = reg_bit_of(LAY, L);
     static_assert(ib >= 0, "the layer's bit is a register bit");
@@ -284,10 +306,10 @@ LDEV void layer(Reg& x, const uint32_t (&G)[3]) {
     static_for<0, 16>([&](auto RI) {
         constexpr unsigned r = decltype(RI)::value;
         if constexpr ((r & half) == 0 && (H < 0 || int(r >> 3) == H)) {
-            constexpr uint64_t A = gf8_matrix(skew_at(kOff, piece_of(LAY, r, 0), L));
-            constexpr uint64_t H0 = gf8_matrix(twist_at(kOff, LAY, r, L, 0));
-            constexpr uint64_t H1 = gf8_matrix(twist_at(kOff, LAY, r, L, 1));
-            constexpr uint64_t H2 = gf8_matrix(twist_at(kOff, LAY, r, L, 2));
+            constexpr uint64_t A = gf8_matrix(skew_at(kOff, piece_of(LAY, r, WV), L));
+            constexpr uint64_t H0 = WB > 0 ? 0 : gf8_matrix(twist_at(kOff, LAY, r, L, 0, WV));
+            constexpr uint64_t H1 = WB > 1 ? 0 : gf8_matrix(twist_at(kOff, LAY, r, L, 1, WV));
+            constexpr uint64_t H2 = gf8_matrix(twist_at(kOff, LAY, r, L, 2, WV));
             uint32_t* a = x[r];
             uint32_t* b = x[r + half];
             if constexpr (kInverse) {  // IFFT_DIT2: y ^= x; x ^= y * skew
@@ -413,6 +435,50 @@ LDEV void exchange(Reg& x, uint8_t* area, unsigned g, unsigned l) {
         for (int k = 0; k < 8; ++k) x[r][k] = y[r][k];
 }
 
+// The workgroup-cooperative tile (WB wave bits, 1 << WB waves): the same
+// exchange through ONE area of the workgroup, because the low WB bits of g are
+// the wave: a register's dwords go to another wave.  A wave has 8 << WB column
+// lanes, so piece p, column l is at byte (64 << WB) p + 8 l (32 column lanes
+// of 8 bytes cover all 64 banks once).  One round is 8 KiB << WB; a barrier
+// between a round's writes and its reads, and one before the next round's
+// writes.  Every wave of the workgroup runs every barrier: nothing here may
+// depend on anything but WB.
+template <int WB>
+constexpr unsigned kBsWgAreaBytes = 128u * (64u << WB);
+template <uint32_t FROM, uint32_t TO, int WB>
+LDEV void exchange_wg(Reg& x, uint8_t* area, unsigned g, unsigned l) {
+#if defined(ABL_XCH) || defined(ABL_LDSX)
+    __syncthreads();
+    return;
+#endif
+    constexpr unsigned kRow = 64u << WB;
+    Reg y;
+    uint8_t* const wbase = area + kRow * piece_of(FROM, 0, g) + 8u * l;
+    uint8_t* const rbase = area + kRow * piece_of(TO, 0, g) + 8u * l;
+    static_for<0, 4>([&](auto Q) {
+        constexpr int q = decltype(Q)::value;
+        static_for<0, 16>([&](auto RI) {
+            constexpr unsigned r = decltype(RI)::value;
+            v2u v;
+            v.x = x[r][2 * q];
+            v.y = x[r][2 * q + 1];
+            *reinterpret_cast<v2u*>(wbase + kRow * piece_of(FROM, r, 0)) = v;
+        });
+        __syncthreads();
+        static_for<0, 16>([&](auto RI) {
+            constexpr unsigned r = decltype(RI)::value;
+            const v2u v = *reinterpret_cast<const v2u*>(rbase + kRow * piece_of(TO, r, 0));
+            y[r][2 * q] = v.x;
+            y[r][2 * q + 1] = v.y;
+        });
+        __syncthreads();
+    });
+#pragma unroll
+    for (int r = 0; r < 16; ++r)
+#pragma unroll
+        for (int k = 0; k < 8; ++k) x[r][k] = y[r][k];
+}
+
 // ---------------------------------------------------------- tile I/O -----
 
 // Where one tile (object, 256-byte column strip) lives for this lane.
@@ -435,17 +501,21 @@ struct BsTile {
     int32_t in_stride, out_stride;
     Off in0, in1, out0, out1;
 };
-template <bool kNarrow>
+// WB wave bits: the strip is 256 << WB bytes over the wave's 8 << WB column
+// lanes l (the same strip for every wave of the workgroup; the waves differ in
+// g), its two segments half a strip apart.
+template <bool kNarrow, int WB = 0>
 LDEV BsTile<kNarrow> bs_tile(const Ff8SlabBatch& b, unsigned t, unsigned strips, unsigned g, unsigned l) {
     using Off = typename BsTile<kNarrow>::Off;
+    constexpr unsigned kStrip = kBsStrip << WB;
     const unsigned obj = t / strips, strip = t - obj * strips;
-    const uint32_t rem = b.nunits * 4u - strip * kBsStrip;  // >= 64 (bytes % 64 == 0)
-    const uint32_t o0 = 16u * l, o1 = 128u + 16u * l;
+    const uint32_t rem = b.nunits * 4u - strip * kStrip;  // >= 64 (bytes % 64 == 0)
+    const uint32_t o0 = 16u * l, o1 = kStrip / 2 + 16u * l;
     const uint32_t s0 = o0 + 16u <= rem ? o0 : 0u, s1 = o1 + 16u <= rem ? o1 : 0u;
     BsTile<kNarrow> T;
     T.in_stride = b.in_stride[obj];
     T.out_stride = b.out_stride[obj];
-    const uint64_t col = uint64_t(strip) * kBsStrip;
+    const uint64_t col = uint64_t(strip) * kStrip;
     T.in = b.in_base[obj] + col;
     T.out = b.out_base[obj] + col;
     const Off pg = Off(piece_of(kLay0, 0, g));  // the lane group's pieces: pg | r
@@ -537,20 +607,47 @@ __device__ uint64_t* g_bs_clock;
 // -------------------------------------------------------------- kernel -----
 
 // One transform direction's low layers (0-2) on half H, and their inverse order.
-template <bool kInverse, int kOff, int H>
+// The layout the low layers end in (and the exchange to kLayT starts from):
+// with two wave bits g bit 1 is a wave bit, so piece bits 1 <-> 5 are not
+// traded by a lane swap and layer 2 runs in kLay1.
+template <int WB>
+constexpr uint32_t kLayLow = WB == 2 ? kLay1 : kLay2;
+template <bool kInverse, int kOff, int H, int WB = 0, unsigned WV = 0>
 LDEV void low_layers(Reg& x, const uint32_t (&G)[3]) {
+    constexpr bool kSwap1 = LAMD_BS_SWAPS && WB < 2;
     if constexpr (kInverse) {
-        layer<true, kOff, 0, kLay0, H>(x, G);
+        layer<true, kOff, 0, kLay0, H, WB, WV>(x, G);
         if constexpr (LAMD_BS_SWAPS) swap_lanes<0, 2, H>(x);
-        layer<true, kOff, 1, kLay1, H>(x, G);
-        if constexpr (LAMD_BS_SWAPS) swap_lanes<1, 1, H>(x);
-        layer<true, kOff, 2, kLay2, H>(x, G);
+        layer<true, kOff, 1, kLay1, H, WB, WV>(x, G);
+        if constexpr (kSwap1) swap_lanes<1, 1, H>(x);
+        layer<true, kOff, 2, kLayLow<WB>, H, WB, WV>(x, G);
     } else {
-        layer<false, kOff, 2, kLay2, H>(x, G);
-        if constexpr (LAMD_BS_SWAPS) swap_lanes<1, 1, H>(x);
-        layer<false, kOff, 1, kLay1, H>(x, G);
+        layer<false, kOff, 2, kLayLow<WB>, H, WB, WV>(x, G);
+        if constexpr (kSwap1) swap_lanes<1, 1, H>(x);
+        layer<false, kOff, 1, kLay1, H, WB, WV>(x, G);
         if constexpr (LAMD_BS_SWAPS) swap_lanes<0, 2, H>(x);
-        layer<false, kOff, 0, kLay0, H>(x, G);
+        layer<false, kOff, 0, kLay0, H, WB, WV>(x, G);
+    }
+}
+// The low layers of wave wv of a workgroup-cooperative tile: one scalar branch
+// to the wave's variant (only the butterflies' constants differ; no barrier
+// inside, so the waves may take different paths).
+template <bool kInverse, int kOff, int H, int WB>
+LDEV void low_layers_of(Reg& x, const uint32_t (&G)[3], unsigned wv) {
+    if constexpr (WB == 0) {
+        low_layers<kInverse, kOff, H>(x, G);
+    } else if constexpr (WB == 1) {
+        if (wv == 0)
+            low_layers<kInverse, kOff, H, 1, 0>(x, G);
+        else
+            low_layers<kInverse, kOff, H, 1, 1>(x, G);
+    } else {
+        switch (wv) {
+            case 0: low_layers<kInverse, kOff, H, 2, 0>(x, G); break;
+            case 1: low_layers<kInverse, kOff, H, 2, 1>(x, G); break;
+            case 2: low_layers<kInverse, kOff, H, 2, 2>(x, G); break;
+            default: low_layers<kInverse, kOff, H, 2, 3>(x, G); break;
+        }
     }
 }
 
@@ -565,24 +662,37 @@ LDEV void low_layers(Reg& x, const uint32_t (&G)[3]) {
 // tile a whole tile ahead, by LDS-DMA into the unused LDS or into spare VGPRs --
 // addresses latency, which is not what binds: the kernel runs at the board's
 // power limit, memory and arithmetic each at full clock alone)
-template <int kForm, bool kNarrow>
-__global__ void __launch_bounds__(64 * kBsWaves) __attribute__((amdgpu_waves_per_eu(LAMD_BS_OCC, LAMD_BS_OCC)))
+//
+// WB > 0, the workgroup-cooperative tile: the 1 << WB waves of a workgroup share
+// ONE tile of 128 pieces x (256 << WB) bytes.  The low WB bits of g are the
+// wave's index, so the low layers are twisted by 3 - WB lane bits only (a code
+// variant per wave, low_layers_of); the exchanges to and from kLayT cross the
+// waves (exchange_wg, barriers).  The tile index, the queue and the loop's exit
+// are then per workgroup: wave 0 asks the queue and publishes the answer
+// through LDS, every wave reads the same word, so all of them take the same
+// next tile or leave together -- no wave may return or loop alone, the others
+// would wait at a barrier for ever.
+template <int kForm, bool kNarrow, int WB = 0>
+__global__ void __launch_bounds__(WB ? (64 << WB) : 64 * kBsWaves) __attribute__((amdgpu_waves_per_eu(LAMD_BS_OCC, LAMD_BS_OCC)))
 k_ff8_bs_slab(Ff8SlabBatch b, uint32_t count, uint32_t strips, uint32_t* q, uint32_t* qclear) {
     constexpr int kOffI = kForm == kFormDenseDec ? -1 : 127;  // IFFT skew base
     constexpr int kOffF = kForm == kFormDenseDec ? 127 : -1;  // FFT skew base
+    constexpr unsigned kTiles = WB ? 1u : unsigned(kBsWaves);  // tiles in flight per workgroup
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     const unsigned wave = threadIdx.x >> 6;
-    const unsigned n = gridDim.x * kBsWaves, total = count * strips;
-    uint8_t* const area = reinterpret_cast<uint8_t*>(lds + wave * kBsAreaDw);
+    const unsigned n = gridDim.x * kTiles, total = count * strips;
+    uint8_t* const area = reinterpret_cast<uint8_t*>(lds + (WB ? 0u : wave * kBsAreaDw));
     // wave-uniform, so that a tile's pointers are scalar loads (off the vector
     // memory counter the piece loads are waited on with)
-    unsigned t = __builtin_amdgcn_readfirstlane(blockIdx.x * kBsWaves + wave);
-    if (t >= total) return;  // waves share nothing
+    unsigned t = __builtin_amdgcn_readfirstlane(WB ? blockIdx.x : blockIdx.x * kBsWaves + wave);
+    if (t >= total) return;  // WB = 0: waves share nothing; WB > 0: the same for the whole workgroup
 #ifdef LAMD_CLOCK
     const uint64_t c0 = __builtin_amdgcn_s_memtime(), r0 = __builtin_amdgcn_s_memrealtime();
     const unsigned t0 = t;
 #endif
-    const unsigned lane = threadIdx.x & 63u, g = lane >> 3, l = lane & 7u;
+    const unsigned lane = threadIdx.x & 63u;
+    const unsigned wv = WB ? __builtin_amdgcn_readfirstlane(wave) : 0u;  // the wave bits of g
+    const unsigned g = ((lane >> (3 + WB)) << WB) | wv, l = lane & ((8u << WB) - 1u);
     // Tile queues (q != null): after the first round (tile = wave index) a wave
     // takes its next tile from the queue of its XCD (workgroups are dealt to
     // the 8 XCDs round robin): tiles n + xq + 8 k, k = that queue's counter.
@@ -594,22 +704,28 @@ k_ff8_bs_slab(Ff8SlabBatch b, uint32_t count, uint32_t strips, uint32_t* q, uint
     if (qclear != nullptr && blockIdx.x == 0 && wave == 0 && lane < 8u) qclear[32u * lane] = 0u;
     const unsigned xq = blockIdx.x & 7u;
     uint32_t* const head = q != nullptr ? q + 32u * xq : nullptr;
+    // WB > 0: the queue's answer, behind the exchange area
+    volatile uint32_t* const slot = lds + kBsWgAreaBytes<WB> / 4;
     const uint32_t G[3] = {(g & 1u) ? ~0u : 0u, (g & 2u) ? ~0u : 0u, (g & 4u) ? ~0u : 0u};
     const XMasks xm;
     Reg x;
-    BsTile<kNarrow> cur = bs_tile<kNarrow>(b, t, strips, g, l);
+    BsTile<kNarrow> cur = bs_tile<kNarrow, WB>(b, t, strips, g, l);
     load_half<0, 8>(x, cur);
     load_half<8, 16>(x, cur);
     for (;;) {
         // the next tile's index, requested a tile ahead (its latency hidden)
         uint32_t kq = 0;
-        if (head != nullptr && lane == 0) kq = __hip_atomic_fetch_add(head, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (head != nullptr && lane == 0 && (WB == 0 || wv == 0))
+            kq = __hip_atomic_fetch_add(head, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #ifndef ABL_ARITH
         transpose_half<0>(x, xm);
-        low_layers<true, kOffI, 0>(x, G);
+        low_layers_of<true, kOffI, 0, WB>(x, G, wv);
         transpose_half<8>(x, xm);
-        low_layers<true, kOffI, 1>(x, G);
-        exchange<kLay2, kLayT>(x, area, g, l);
+        low_layers_of<true, kOffI, 1, WB>(x, G, wv);
+        if constexpr (WB)
+            exchange_wg<kLayLow<WB>, kLayT, WB>(x, area, g, l);
+        else
+            exchange<kLay2, kLayT>(x, area, g, l);
         layer<true, kOffI, 3, kLayT>(x, G);
         layer<true, kOffI, 4, kLayT>(x, G);
         layer<true, kOffI, 5, kLayT>(x, G);
@@ -617,22 +733,36 @@ k_ff8_bs_slab(Ff8SlabBatch b, uint32_t count, uint32_t strips, uint32_t* q, uint
         layer<false, kOffF, 5, kLayT>(x, G);
         layer<false, kOffF, 4, kLayT>(x, G);
         layer<false, kOffF, 3, kLayT>(x, G);
-        exchange<kLayT, kLay2>(x, area, g, l);
+        if constexpr (WB) {
+            // published by the exchange's first barrier; the slot is written
+            // again a whole exchange (8 barriers) after every wave has read it
+            if (head != nullptr && lane == 0 && wv == 0) *slot = kq;
+            exchange_wg<kLayT, kLayLow<WB>, WB>(x, area, g, l);
+            if (head != nullptr) kq = *slot;
+        } else {
+            exchange<kLayT, kLay2>(x, area, g, l);
+        }
 #else
 #pragma unroll
         for (int r = 0; r < 16; ++r) pin8(x[r]);
+        if constexpr (WB) {
+            if (head != nullptr && lane == 0 && wv == 0) *slot = kq;
+            __syncthreads();
+            if (head != nullptr) kq = *slot;
+            __syncthreads();
+        }
 #endif
         const unsigned tn = head != nullptr ? n + xq + 8u * __builtin_amdgcn_readfirstlane(kq) : t + n;
         const bool more = tn < total;
-        const BsTile<kNarrow> nxt = bs_tile<kNarrow>(b, more ? tn : t, strips, g, l);
+        const BsTile<kNarrow> nxt = bs_tile<kNarrow, WB>(b, more ? tn : t, strips, g, l);
 #ifndef ABL_ARITH
-        low_layers<false, kOffF, 0>(x, G);
+        low_layers_of<false, kOffF, 0, WB>(x, G, wv);
         transpose_half<0>(x, xm);
 #endif
         store_half<0>(x, cur);
         if (more) load_half<0, 8>(x, nxt);
 #ifndef ABL_ARITH
-        low_layers<false, kOffF, 1>(x, G);
+        low_layers_of<false, kOffF, 1, WB>(x, G, wv);
         transpose_half<8>(x, xm);
 #endif
         store_half<8>(x, cur);
@@ -656,17 +786,67 @@ bool ff8_bs_supported(unsigned T, unsigned K, unsigned R, unsigned nchunks) {
     return T == 7 && K == 128 && R == 128 && nchunks == 1;
 }
 
+// Wave bits of the launch's tile.  The workgroup-cooperative tile does the same
+// work per wave and per workgroup as four (two) independent waves' tiles, on
+// the same grid, so it needs no minimum tile count; what it can lose is lanes
+// past the piece's end, since its strips are 256 << WB bytes.  It runs when the
+// pieces, padded to whole strips, are at most 1/4 longer than padded to
+// 256-byte strips (pieces shorter than a strip never are): at 18% more it still
+// measured 20% faster than the one-wave tile (64 objects of 4160-byte pieces,
+// DESIGN.md section 7.8).  Experiment builds:
+// LEO_AMD_FF8_BS_WAVES = 1 | 2 | 4 forces the waves per tile at every size.
+#ifndef LAMD_BS_WB
+#define LAMD_BS_WB 2  // the product's workgroup-cooperative tile (0: none)
+#endif
+namespace {
+int bs_wave_bits(uint32_t bytes) {
+#if LAMD_EXPERIMENT_ENV
+    static const int forced = [] {
+        const char* e = std::getenv("LEO_AMD_FF8_BS_WAVES");
+        return !e ? -1 : e[0] == '1' ? 0 : e[0] == '2' ? 1 : e[0] == '4' ? 2 : -1;
+    }();
+    if (forced >= 0) return forced;
+#endif
+    constexpr int WB = LAMD_BS_WB;
+    if (WB == 0) return 0;
+    const uint64_t strip = kBsStrip << WB;
+    const uint64_t pad = (bytes + strip - 1) / strip * strip, pad0 = (uint64_t(bytes) + kBsStrip - 1) / kBsStrip * kBsStrip;
+    return pad * 4u <= pad0 * 5u ? WB : 0;
+}
+template <int kForm, int WB>
+const void* bs_kernel_wg() {
+    // product builds hold the one cooperative tile they use
+    if constexpr (LAMD_EXPERIMENT_ENV || WB == LAMD_BS_WB)
+        return reinterpret_cast<const void*>(&k_ff8_bs_slab<kForm, true, WB>);
+    else
+        return nullptr;
+}
+}  // namespace
+
 hipError_t launch_ff8_bs_slab(const Ff8SlabBatch& b, unsigned count, int form, hipStream_t s, unsigned cus,
                               uint32_t* q, uint32_t* qclear) {
     if (count == 0 || count > kSlabObjs || (b.nunits * 4u) % 64u != 0 || b.K != 128 || b.R != 128)
         return hipErrorInvalidValue;
     if (form != kFormDenseEnc && form != kFormDenseDec) return hipErrorInvalidValue;
     cus = std::max(cus, 1u);
-    uint32_t strips = (b.nunits * 4u + kBsStrip - 1) / kBsStrip;
+    // 32-bit lane offsets when every slab's lane offsets (up to 127 strides + a
+    // strip) fit them; the cooperative tile is built for those only
+    bool narrow = true, narrow_wg = true;
+    for (unsigned o = 0; o < count; ++o)
+        for (const int32_t st : {b.in_stride[o], b.out_stride[o]}) {
+            narrow = narrow && st >= 0 && uint64_t(st) * 128u + kBsStrip <= (uint64_t(1) << 32);
+            narrow_wg = narrow_wg && st >= 0 && uint64_t(st) * 128u + (kBsStrip << 2) <= (uint64_t(1) << 32);
+        }
+    const int wb = narrow_wg ? bs_wave_bits(b.nunits * 4u) : 0;
+    const uint32_t strip = kBsStrip << wb;
+    uint32_t strips = (b.nunits * 4u + strip - 1) / strip;
     uint32_t cnt = count;
     const unsigned total = cnt * strips;
-    const unsigned blocks = std::min<unsigned>((total + kBsWaves - 1) / kBsWaves, cus * kBsBlocksPerCu);
-    const size_t lds = size_t(kBsWaves) * kBsAreaDw * 4;
+    // workgroups: wb = 0, kBsWaves tiles each; wb > 0, one tile of 1 << wb waves
+    const unsigned tiles_wg = wb ? 1u : unsigned(kBsWaves), waves_wg = wb ? 1u << wb : unsigned(kBsWaves);
+    const unsigned per_cu = wb ? 4u * LAMD_BS_OCC >> wb : kBsBlocksPerCu;
+    const unsigned blocks = std::min<unsigned>((total + tiles_wg - 1) / tiles_wg, cus * per_cu);
+    const size_t lds = wb ? size_t(8192u << wb) + 16 : size_t(kBsWaves) * kBsAreaDw * 4;
 #if LAMD_BS_QUEUE == 0
     q = qclear = nullptr;
 #endif
@@ -675,18 +855,19 @@ hipError_t launch_ff8_bs_slab(const Ff8SlabBatch& b, unsigned count, int form, h
     // next launch's set is still cleared (Workspace::bs_queue alternates them)
     if (blocks < 8) q = nullptr;
     void* params[] = {const_cast<Ff8SlabBatch*>(&b), &cnt, &strips, &q, &qclear};
-    // 32-bit lane offsets when every slab's lane offsets (up to 127 strides + a
-    // strip) fit them
-    bool narrow = true;
-    for (unsigned o = 0; o < count; ++o)
-        for (const int32_t st : {b.in_stride[o], b.out_stride[o]})
-            narrow = narrow && st >= 0 && uint64_t(st) * 128u + kBsStrip <= (uint64_t(1) << 32);
-    const void* fn = form == kFormDenseDec
-                         ? (narrow ? reinterpret_cast<const void*>(&k_ff8_bs_slab<kFormDenseDec, true>)
-                                   : reinterpret_cast<const void*>(&k_ff8_bs_slab<kFormDenseDec, false>))
-                         : (narrow ? reinterpret_cast<const void*>(&k_ff8_bs_slab<kFormDenseEnc, true>)
-                                   : reinterpret_cast<const void*>(&k_ff8_bs_slab<kFormDenseEnc, false>));
-    return hipLaunchKernel(fn, dim3(blocks), dim3(64 * kBsWaves), params, lds, s);
+    const bool dec = form == kFormDenseDec;
+    const void* fn = nullptr;
+    if (wb == 2)
+        fn = dec ? bs_kernel_wg<kFormDenseDec, 2>() : bs_kernel_wg<kFormDenseEnc, 2>();
+    else if (wb == 1)
+        fn = dec ? bs_kernel_wg<kFormDenseDec, 1>() : bs_kernel_wg<kFormDenseEnc, 1>();
+    else
+        fn = dec ? (narrow ? reinterpret_cast<const void*>(&k_ff8_bs_slab<kFormDenseDec, true>)
+                           : reinterpret_cast<const void*>(&k_ff8_bs_slab<kFormDenseDec, false>))
+                 : (narrow ? reinterpret_cast<const void*>(&k_ff8_bs_slab<kFormDenseEnc, true>)
+                           : reinterpret_cast<const void*>(&k_ff8_bs_slab<kFormDenseEnc, false>));
+    if (fn == nullptr) return hipErrorInvalidValue;  // a tile this build does not hold
+    return hipLaunchKernel(fn, dim3(blocks), dim3(64 * waves_wg), params, lds, s);
 }
 
 }  // namespace lamd
