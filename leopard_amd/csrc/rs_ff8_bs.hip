@@ -13,7 +13,9 @@
 // the 8 x 8 GF(2) matrix of c applied to the planes: plane i of x takes the XOR
 // of the planes j of y that row i selects.  Every skew of the dense tile is
 // known at compile time (gf8_const.h), so most butterflies compile to a fixed
-// XOR network (~4x cheaper than the byte form, tools/ubench_bitslice8.hip).
+// XOR network (~4x cheaper than the byte form, tools/ubench_bitslice8.hip),
+// synthesized with shared subexpressions (gf8_net.h; the layouts and every
+// butterfly's constants: bs_layout.h).
 //
 // Tile: ONE wave owns the whole 128-piece transform over a 256-byte column
 // strip of every piece.  Lane = 8 * g + l: lane group g (8 groups), lane l of
@@ -48,7 +50,9 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "bs_layout.h"
 #include "gf8_const.h"
+#include "gf8_net.h"
 #include "rs_args.h"
 
 namespace lamd {
@@ -141,23 +145,6 @@ LDEV void transpose8(uint32_t* v, const XMasks& m) {
 }
 
 LDEV uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) { return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96); }
-// acc ^ (XOR of the planes y[j] with bit j of `row` set), as 3-input XORs
-template <unsigned row, int J = 0>
-LDEV uint32_t fold(uint32_t acc, const uint32_t* y) {
-    if constexpr (J >= 8 || (row >> J) == 0) {
-        return acc;
-    } else if constexpr (((row >> J) & 1u) == 0) {
-        return fold<row, J + 1>(acc, y);
-    } else {
-        constexpr unsigned rest = row & ~((2u << J) - 1u);  // bits above J
-        if constexpr (rest == 0) {
-            return acc ^ y[J];
-        } else {
-            constexpr int K = __builtin_ctz(rest);
-            return fold<row & ~((2u << K) - 1u), K + 1>(xor3(acc, y[J], y[K]), y);
-        }
-    }
-}
 // Keep a value materialised here: the networks are all XORs, and without a
 // fence the compiler reassociates them across butterflies and layers into
 // long-lived shared subexpressions (200+ VGPRs instead of the tile's 128).
@@ -166,133 +153,108 @@ LDEV void pin8(uint32_t* v) {
     for (int k = 0; k < 8; ++k) asm volatile("" : "+v"(v[k]));
 }
 
-// x ^= M * y (M compile time: the multiply by a constant as an XOR network)
-template <uint64_t M>
-LDEV void mac(uint32_t* x, const uint32_t* y) {
-    static_for<0, 8>([&](auto I) {
-        constexpr int i = decltype(I)::value;
-        constexpr unsigned row = unsigned(M >> (8 * i)) & 0xFFu;
-        if constexpr (row != 0) x[i] = fold<row>(x[i], y);
-    });
+// Variable V of a network (gf8_net.h): a plane of y or a temporary.
+template <int V>
+LDEV uint32_t net_var(const uint32_t* y, const uint32_t* t) {
+    if constexpr (V < 8)
+        return y[V];
+    else
+        return t[V - 8];
 }
-// x ^= (M * y) & g  (g: a per-lane all-ones / all-zeros mask)
-template <uint64_t M>
-LDEV void mac_masked(uint32_t* x, const uint32_t* y, uint32_t g) {
-#ifdef ABL_MASKED
-    return;
-#endif
-    static_for<0, 8>([&](auto I) {
-        constexpr int i = decltype(I)::value;
-        constexpr unsigned row = unsigned(M >> (8 * i)) & 0xFFu;
-        if constexpr (row != 0) {
-            constexpr int J = __builtin_ctz(row);
-            x[i] = xor_and(x[i], fold<(row & ~(1u << J))>(y[J], y), g);
+// acc ^ (XOR of the variables of `mask`), as 3-input XORs
+template <uint32_t mask>
+LDEV uint32_t fold(uint32_t acc, const uint32_t* y, const uint32_t* t) {
+    if constexpr (mask == 0) {
+        return acc;
+    } else {
+        constexpr int J = __builtin_ctz(mask);
+        constexpr uint32_t rest = mask & (mask - 1u);
+        if constexpr (rest == 0) {
+            return acc ^ net_var<J>(y, t);
+        } else {
+            constexpr int K = __builtin_ctz(rest);
+            return fold<(rest & (rest - 1u))>(xor3(acc, net_var<J>(y, t), net_var<K>(y, t)), y, t);
         }
+    }
+}
+// XOR of the variables of `mask` (not empty)
+template <uint32_t mask>
+LDEV uint32_t fold_of(const uint32_t* y, const uint32_t* t) {
+    return fold<(mask & (mask - 1u))>(net_var<__builtin_ctz(mask)>(y, t), y, t);
+}
+
+// x ^= A y ^ ((H0 y) & G[0]) ^ ((H1 y) & G[1]) ^ ((H2 y) & G[2]): the constant
+// and the twists of one butterfly (compile time; G: per-lane all-ones /
+// all-zeros masks) as ONE synthesized XOR network, whose temporaries the four
+// products share.  The temporaries die here.
+template <uint64_t A, uint64_t H0 = 0, uint64_t H1 = 0, uint64_t H2 = 0>
+LDEV void mac(uint32_t* x, const uint32_t* y, const uint32_t (&G)[3]) {
+    using N = Gf8NetOf<A, H0, H1, H2>;
+    uint32_t t[kNetMaxTemps];
+    static_for<0, N::net.ntemp>([&](auto K) {
+        constexpr int k = decltype(K)::value;
+        t[k] = fold_of<N::net.temp[k]>(y, t);
+    });
+    static_for<0, 8>([&](auto I) {
+        constexpr int i = decltype(I)::value;
+        x[i] = fold<N::net.row[0][i]>(x[i], y, t);
+        static_for<1, kNetMats>([&](auto MI) {
+            constexpr int m = decltype(MI)::value;
+            if constexpr (N::net.row[m][i] != 0) x[i] = xor_and(x[i], fold_of<N::net.row[m][i]>(y, t), G[m - 1]);
+        });
     });
 }
 
-// ------------------------------------------------------------ skews --------
-
-constexpr unsigned sidx(unsigned p, unsigned l) { return ((p >> l) | 1u) << l; }
-constexpr unsigned skew_at(int off, unsigned p, unsigned l) { return gf8_skew(off + int(sidx(p, l))); }
-
-// ----------------------------------------------------------- layouts -------
-
-// A layout says which piece-index bit each register-index bit (4) and each
-// lane-group bit (3, g = lane >> 3) holds: piece(r, g) = the OR of bit i of r
-// at position rb[i] and bit j of g at position gb[j].  Packed into a template
-// argument: rb[i] in bits 3 i .. 3 i + 2, gb[j] in bits 12 + 3 j ...
-constexpr uint32_t lay(unsigned r0, unsigned r1, unsigned r2, unsigned r3, unsigned g0, unsigned g1, unsigned g2) {
-    return r0 | r1 << 3 | r2 << 6 | r3 << 9 | g0 << 12 | g1 << 15 | g2 << 18;
-}
-constexpr unsigned lay_rb(uint32_t L, unsigned i) { return (L >> (3 * i)) & 7u; }
-constexpr unsigned lay_gb(uint32_t L, unsigned j) { return (L >> (12 + 3 * j)) & 7u; }
-constexpr unsigned piece_of(uint32_t L, unsigned r, unsigned g) {
-    unsigned p = 0;
-    for (unsigned i = 0; i < 4; ++i) p |= ((r >> i) & 1u) << lay_rb(L, i);
-    for (unsigned j = 0; j < 3; ++j) p |= ((g >> j) & 1u) << lay_gb(L, j);
-    return p;
-}
-constexpr int reg_bit_of(uint32_t L, unsigned pbit) {
-    for (unsigned i = 0; i < 4; ++i)
-        if (lay_rb(L, i) == pbit) return int(i);
-    return -1;
-}
-constexpr bool lay_ok(uint32_t L) {
-    unsigned seen = 0;
-    for (unsigned i = 0; i < 4; ++i) seen |= 1u << lay_rb(L, i);
-    for (unsigned j = 0; j < 3; ++j) seen |= 1u << lay_gb(L, j);
-    return seen == 127u;
-}
-
-// A layer-l skew depends on the piece bits above l only (sidx).  Those held
-// by lane-group bits make it vary over the wave; it is affine in them
-// (FFTInitialize builds FFTSkew[first + k 2^(l+1)] as the XOR of one generator
-// per bit of k, LeopardFF8.cpp:505-514), so
-//   c(r, g) * y = A_r * y  ^  sum over g bits j above l of  (g_j ? H_j * y : 0)
-// with A_r = the skew of piece(r, 0) and H_j = the generator of bit gb[j]: the
-// "twist", selected per lane by the all-ones masks G[j] (checked here for every
-// layout the kernel uses).
-//
-// Wave bits (WB, the workgroup-cooperative tile below): the low WB bits of g
-// are not lane bits but the wave's index in its workgroup, wv.  They are
-// wave-uniform, so a code variant per wv folds them into A_r = the skew of
-// piece(r, wv) and only the bits j >= WB are twisted.
-constexpr unsigned twist_at(int off, uint32_t L, unsigned r, unsigned l, unsigned j, unsigned wv = 0) {
-    const unsigned p = piece_of(L, r, wv);
-    return lay_gb(L, j) > l ? skew_at(off, p | (1u << lay_gb(L, j)), l) ^ skew_at(off, p, l) : 0u;
-}
-constexpr bool affine_ok(uint32_t L, unsigned l, unsigned WB = 0) {
-    for (int off : {-1, 127})
-        for (unsigned r = 0; r < 16; ++r)
-            for (unsigned g = 0; g < 8; ++g) {
-                const unsigned wv = g & ((1u << WB) - 1u);
-                unsigned v = skew_at(off, piece_of(L, r, wv), l);
-                for (unsigned j = WB; j < 3; ++j)
-                    if ((g >> j) & 1u) v ^= twist_at(off, L, r, l, j, wv);
-                if (v != skew_at(off, piece_of(L, r, g), l)) return false;
-            }
-    return true;
-}
-
-// Layouts of the tile (LAMD_BS_SWAPS = 1, the default):
-//   kLay0 (load / store, layer 0): registers = piece bits 0-3, lane groups 6, 5, 4;
-//   kLay1 (layer 1): piece bit 0 <-> 4 exchanged (v_permlane32_swap: g bit 2 is lane bit 5);
-//   kLay2 (layer 2): piece bit 1 <-> 5 exchanged (v_permlane16_swap: g bit 1 is lane bit 4);
-//   kLayT (layers 3-6): piece bit 2 <-> 6 exchanged through LDS (g bit 0 is lane bit 3).
-// Layer l then varies over the lane groups in 3, 2, 1, 0 bits (l = 0, 1, 2, >= 3),
-// the fewest any 4-register-bit layout allows: 6 twisted (layer, bit) pairs per
-// transform instead of 9.  LAMD_BS_SWAPS = 0 is the round-5 tile: layers 0-2 in
-// kLay0 (lane groups 4, 5, 6), one LDS exchange of all three bits to kLayT.
 #ifndef LAMD_BS_QUEUE
 #define LAMD_BS_QUEUE 1  // tile queues (0: every wave codes tiles i, i + n, i + 2 n, ...)
 #endif
-#ifndef LAMD_BS_SWAPS
-#define LAMD_BS_SWAPS 1
-#endif
-#if LAMD_BS_SWAPS
-constexpr uint32_t kLay0 = lay(0, 1, 2, 3, 6, 5, 4);
-constexpr uint32_t kLay1 = lay(4, 1, 2, 3, 6, 5, 0);
-constexpr uint32_t kLay2 = lay(4, 5, 2, 3, 6, 1, 0);
-constexpr uint32_t kLayT = lay(4, 5, 6, 3, 2, 1, 0);
-#else
-constexpr uint32_t kLay0 = lay(0, 1, 2, 3, 4, 5, 6);
-constexpr uint32_t kLay1 = kLay0;
-constexpr uint32_t kLay2 = kLay0;
-constexpr uint32_t kLayT = lay(3, 4, 5, 6, 0, 1, 2);
-#endif
-static_assert(lay_ok(kLay0) && lay_ok(kLay1) && lay_ok(kLay2) && lay_ok(kLayT), "layouts are bit permutations");
-static_assert(affine_ok(kLay0, 0) && affine_ok(kLay1, 1) && affine_ok(kLay2, 2), "skews are affine in the lane-group bits");
-// the workgroup-cooperative tiles: two waves (g bit 0 = piece bit 6 is the wave)
-// run the same layouts; four waves (g bits 0, 1 = piece bits 6, 5) have no lane
-// bit to trade for piece bit 1 and run layer 2 in kLay1
-static_assert(affine_ok(kLay0, 0, 1) && affine_ok(kLay1, 1, 1) && affine_ok(kLay2, 2, 1), "two-wave tile: every wave's variant");
-static_assert(affine_ok(kLay0, 0, 2) && affine_ok(kLay1, 1, 2) && affine_ok(kLay1, 2, 2), "four-wave tile: every wave's variant");
-static_assert(reg_bit_of(kLay1, 2) == 2 && reg_bit_of(kLay1, 3) == 3 && reg_bit_of(kLay2, 3) == 3, "register bit 3 = piece bit 3 in every low layout");
 
 // ----------------------------------------------------------- butterflies ---
 
 using Reg = uint32_t[16][8];
+
+LDEV void xor8(uint32_t* x, const uint32_t* y) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) x[k] ^= y[k];
+}
+LDEV void swap8(uint32_t* x, uint32_t* y) {  // a renaming: the indices are compile time
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const uint32_t v = x[k];
+        x[k] = y[k];
+        y[k] = v;
+    }
+}
+// One butterfly with the multiplier c(g) = M.A ^ the twists M.H the masks G select:
+//   FFT_DIT2   a' = a ^ c b, b' = b ^ a'     or, the same,  b' = a ^ (c ^ 1) b, a' = b' ^ b;
+//   IFFT_DIT2  b' = a ^ b,   a' = a ^ c b'   or, the same,  b' = a ^ b, a' = b ^ (c ^ 1) b'.
+// The second forms leave a' and b' in each other's registers, which costs
+// nothing (register names are compile time), so the butterfly runs the network
+// of c or of c ^ 1, whichever has fewer gates (bs_alt_form).
+template <bool kInverse, uint64_t A, uint64_t H0, uint64_t H1, uint64_t H2>
+LDEV void butterfly(uint32_t* a, uint32_t* b, const uint32_t (&G)[3]) {
+#ifdef ABL_MASKED
+    constexpr BsMats M = {A, {0, 0, 0}};
+#else
+    constexpr BsMats M = {A, {H0, H1, H2}};
+#endif
+    // bs_alt_form(M), by the networks this file instantiates anyway
+    constexpr bool kAlt = LAMD_BS_ALT && Gf8NetOf<(M.A ^ kGf8Identity), M.H[0], M.H[1], M.H[2]>::net.gates <
+                                             Gf8NetOf<M.A, M.H[0], M.H[1], M.H[2]>::net.gates;
+    if constexpr (!kAlt) {
+        if constexpr (kInverse) xor8(b, a);
+        mac<M.A, M.H[0], M.H[1], M.H[2]>(a, b, G);
+        if constexpr (!kInverse) xor8(b, a);
+    } else if constexpr (kInverse) {
+        xor8(a, b);
+        mac<(M.A ^ kGf8Identity), M.H[0], M.H[1], M.H[2]>(b, a, G);
+        swap8(a, b);
+    } else {
+        mac<(M.A ^ kGf8Identity), M.H[0], M.H[1], M.H[2]>(a, b, G);
+        xor8(b, a);
+        swap8(a, b);
+    }
+}
 
 // Layer L in layout LAY: the pairs (r, r + 2^i) over the register bit i that
 // holds piece bit L, restricted to the half of register bit 3 = H (H < 0: all
@@ -306,26 +268,10 @@ LDEV void layer(Reg& x, const uint32_t (&G)[3]) {
     static_for<0, 16>([&](auto RI) {
         constexpr unsigned r = decltype(RI)::value;
         if constexpr ((r & half) == 0 && (H < 0 || int(r >> 3) == H)) {
-            constexpr uint64_t A = gf8_matrix(skew_at(kOff, piece_of(LAY, r, WV), L));
-            constexpr uint64_t H0 = WB > 0 ? 0 : gf8_matrix(twist_at(kOff, LAY, r, L, 0, WV));
-            constexpr uint64_t H1 = WB > 1 ? 0 : gf8_matrix(twist_at(kOff, LAY, r, L, 1, WV));
-            constexpr uint64_t H2 = gf8_matrix(twist_at(kOff, LAY, r, L, 2, WV));
-            uint32_t* a = x[r];
-            uint32_t* b = x[r + half];
-            if constexpr (kInverse) {  // IFFT_DIT2: y ^= x; x ^= y * skew
-#pragma unroll
-                for (int k = 0; k < 8; ++k) b[k] ^= a[k];
-            }
-            mac<A>(a, b);
-            if constexpr (H0 != 0) mac_masked<H0>(a, b, G[0]);
-            if constexpr (H1 != 0) mac_masked<H1>(a, b, G[1]);
-            if constexpr (H2 != 0) mac_masked<H2>(a, b, G[2]);
-            if constexpr (!kInverse) {  // FFT_DIT2: x ^= y * skew; y ^= x
-#pragma unroll
-                for (int k = 0; k < 8; ++k) b[k] ^= a[k];
-            }
-            pin8(a);
-            pin8(b);
+            constexpr BsMats M = bs_mats(kOff, LAY, r, L, WB, WV);
+            butterfly<kInverse, M.A, M.H[0], M.H[1], M.H[2]>(x[r], x[r + half], G);
+            pin8(x[r]);
+            pin8(x[r + half]);
             bs_fence_every<LAMD_BS_BFENCE>(int(r));
         }
     });
@@ -335,22 +281,17 @@ LDEV void layer(Reg& x, const uint32_t (&G)[3]) {
 // y1 = y ^ x, x2 = x ^ (c1 + c2) y1, y2 = y1 ^ x2.  Piece bit 6 is a register
 // bit of kLayT and the skews of layer 6 are the same for every pair.
 template <int kOffI, int kOffF>
-LDEV void fused_top(Reg& x) {
+LDEV void fused_top(Reg& x, const uint32_t (&G)[3]) {
     constexpr int ib = reg_bit_of(kLayT, 6);
     constexpr unsigned half = 1u << ib;
     constexpr uint64_t E = gf8_matrix(skew_at(kOffI, 64, 6) ^ skew_at(kOffF, 64, 6));
     static_for<0, 16>([&](auto RI) {
         constexpr unsigned r = decltype(RI)::value;
         if constexpr ((r & half) == 0) {
-            uint32_t* a = x[r];
-            uint32_t* b = x[r + half];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) b[k] ^= a[k];
-            mac<E>(a, b);
-#pragma unroll
-            for (int k = 0; k < 8; ++k) b[k] ^= a[k];
-            pin8(a);
-            pin8(b);
+            xor8(x[r + half], x[r]);
+            butterfly<false, E, 0, 0, 0>(x[r], x[r + half], G);
+            pin8(x[r]);
+            pin8(x[r + half]);
             bs_fence_every<LAMD_BS_BFENCE>(int(r));
         }
     });
@@ -606,12 +547,8 @@ __device__ uint64_t* g_bs_clock;
 
 // -------------------------------------------------------------- kernel -----
 
-// One transform direction's low layers (0-2) on half H, and their inverse order.
-// The layout the low layers end in (and the exchange to kLayT starts from):
-// with two wave bits g bit 1 is a wave bit, so piece bits 1 <-> 5 are not
-// traded by a lane swap and layer 2 runs in kLay1.
-template <int WB>
-constexpr uint32_t kLayLow = WB == 2 ? kLay1 : kLay2;
+// One transform direction's low layers (0-2) on half H, and their inverse order
+// (kLayLow<WB>, bs_layout.h: the layout they end in).
 template <bool kInverse, int kOff, int H, int WB = 0, unsigned WV = 0>
 LDEV void low_layers(Reg& x, const uint32_t (&G)[3]) {
     constexpr bool kSwap1 = LAMD_BS_SWAPS && WB < 2;
@@ -729,7 +666,7 @@ k_ff8_bs_slab(Ff8SlabBatch b, uint32_t count, uint32_t strips, uint32_t* q, uint
         layer<true, kOffI, 3, kLayT>(x, G);
         layer<true, kOffI, 4, kLayT>(x, G);
         layer<true, kOffI, 5, kLayT>(x, G);
-        fused_top<kOffI, kOffF>(x);
+        fused_top<kOffI, kOffF>(x, G);
         layer<false, kOffF, 5, kLayT>(x, G);
         layer<false, kOffF, 4, kLayT>(x, G);
         layer<false, kOffF, 3, kLayT>(x, G);
