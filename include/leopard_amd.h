@@ -128,6 +128,77 @@ LEO_EXPORT LeopardResult leo_amd_update_slice(
     unsigned changed_count, const unsigned* changed_index,
     const void* const* delta_data, void** recovery_data);
 
+/* Rebuild: regenerate every piece a failed node held, lost originals and lost
+ * recovery pieces alike, in the decode pass.  The decode transform is
+ * symmetric in the codeword positions: after it, the erased symbol of any
+ * erased position is at hand, a recovery position as well as an original one,
+ * so lost recovery pieces need no second pass over the originals (leo_decode
+ * followed by a full leo_encode).
+ *
+ * original_data[i] == NULL marks a lost original; it is written to
+ * work_data[i].  work_data[i] of a received original is neither read nor
+ * written and may be NULL: unlike leo_decode, repair writes lost pieces only
+ * and copies nothing when no original is lost.
+ * recovery_data[j] == NULL marks a lost recovery piece.  It is requested when
+ * recovery_out[j] != NULL, and only then is it written; a NULL recovery_out[j]
+ * of a lost piece means "not wanted" (only one node's pieces are being
+ * rebuilt).  recovery_out[j] of a received piece is ignored and never written.
+ *
+ * For consistent input (the received pieces come from one leo_encode codeword)
+ * every written work_data[i] equals the original and every written
+ * recovery_out[j] equals leo_encode's recovery piece j, bit for bit.  For
+ * inconsistent input the lost originals are still bit-identical to
+ * leo_decode's output; the rebuilt recovery pieces are unspecified.
+ *
+ * work_count is as for leo_decode (leo_decode_work_count) and checked the same
+ * way.  All pieces are of one kind: device memory (on the calling thread's
+ * stream, honouring leo_amd_set_stream / set_async / set_device) or host
+ * memory (registered ranges in place, pageable memory staged: inputs are the
+ * received pieces, outputs the lost originals, then the requested recovery
+ * pieces; the call returns when the results are in host memory; the columns
+ * fan out as for leo_decode, leo_amd_set_fanout).  Outputs must not overlap
+ * inputs or each other (not checked).
+ *
+ * Results, in this order: Leopard_InvalidSize (slice form: the slice checks of
+ * leo_amd_decode_slice); Leopard_InvalidCounts (recovery_count 0 or >
+ * original_count); Leopard_InvalidInput for a NULL array (leo_amd_last_error()
+ * names it); Leopard_CallInitialize; Leopard_NeedMoreData (fewer recovery
+ * pieces received than originals lost, as leo_decode: lost originals + lost
+ * recovery > recovery_count); on the general path (original_count > 1,
+ * recovery_count > 1) Leopard_InvalidCounts for work_count != n, then
+ * Leopard_TooMuchData for n > 65536; Leopard_InvalidInput for a lost original
+ * whose work_data[i] is NULL.  Nothing lost or nothing requested returns
+ * Leopard_Success and touches nothing.
+ *
+ * original_count == 1: every piece is a copy of the one original (from the
+ * original if received, else from the last received recovery piece).
+ * recovery_count == 1: a lost recovery_data[0] is the XOR of all originals.
+ *
+ * LEO_AMD_REPAIR_COMPOSE=1 (environment, read once) forces the composition the
+ * call replaces -- the decoder, then the encoder over received and rebuilt
+ * originals with unrequested rows in scratch -- for comparison. */
+LEO_EXPORT LeopardResult leo_amd_repair(
+    uint64_t buffer_bytes, unsigned original_count, unsigned recovery_count, unsigned work_count,
+    const void* const* original_data, const void* const* recovery_data,
+    void** work_data, void** recovery_out);
+
+/* The same over bytes [byte_offset, byte_offset + slice_bytes) of each piece. */
+LEO_EXPORT LeopardResult leo_amd_repair_slice(
+    uint64_t buffer_bytes, uint64_t byte_offset, uint64_t slice_bytes,
+    unsigned original_count, unsigned recovery_count, unsigned work_count,
+    const void* const* original_data, const void* const* recovery_data,
+    void** work_data, void** recovery_out);
+
+/* object_count objects of one shape, each with the semantics of one
+ * leo_amd_repair call; objects may differ in pattern and in what they request.
+ * Every object is validated first: the first failing object's result is
+ * returned and nothing runs.  Device-resident GF(2^8) objects (n <= 256) on one
+ * device run as one launch per 256 objects; other batches object by object. */
+LEO_EXPORT LeopardResult leo_amd_repair_batch(
+    unsigned object_count, uint64_t buffer_bytes, unsigned original_count, unsigned recovery_count,
+    unsigned work_count, const void* const* const* original_data, const void* const* const* recovery_data,
+    void** const* work_data, void** const* recovery_out);
+
 /* Caller-registered host memory: pins [ptr, ptr + bytes) and maps it for
  * every device.  leo_encode / leo_decode calls whose host pieces all lie in
  * registered ranges run the kernels on them in place (reads and writes over

@@ -34,7 +34,9 @@ LEO_VERSION = 2
 __all__ = [
     "LEO_VERSION", "LeopardResult", "leo_init", "leo_result_string", "leo_encode_work_count", "leo_encode",
     "leo_decode_work_count", "leo_decode", "leo_amd_encode_slice", "leo_amd_decode_slice", "leo_amd_encode_batch",
-    "leo_amd_decode_batch", "leo_amd_update", "leo_amd_update_slice", "UPDATE_MAX_CHANGED", "update", "register_host", "unregister_host", "set_fanout", "set_stream", "release_stream",
+    "leo_amd_decode_batch", "leo_amd_update", "leo_amd_update_slice", "UPDATE_MAX_CHANGED", "update",
+    "leo_amd_repair", "leo_amd_repair_slice", "leo_amd_repair_batch", "repair",
+    "register_host", "unregister_host", "set_fanout", "set_stream", "release_stream",
     "set_async", "set_device", "device_count", "table", "last_error", "encode", "decode", "LIB_PATH", "lib",
 ]
 
@@ -74,6 +76,9 @@ def _load():
         "leo_amd_decode_batch": (i, [u, u64, u, u, u, ctypes.POINTER(pp), ctypes.POINTER(pp), ctypes.POINTER(pp)]),
         "leo_amd_update": (i, [u64, u, u, u, ctypes.POINTER(u), pp, pp]),
         "leo_amd_update_slice": (i, [u64, u64, u64, u, u, u, ctypes.POINTER(u), pp, pp]),
+        "leo_amd_repair": (i, [u64, u, u, u, pp, pp, pp, pp]),
+        "leo_amd_repair_slice": (i, [u64, u64, u64, u, u, u, pp, pp, pp, pp]),
+        "leo_amd_repair_batch": (i, [u, u64, u, u, u] + [ctypes.POINTER(pp)] * 4),
         "leo_amd_register_host": (i, [vp, u64]),
         "leo_amd_unregister_host": (i, [vp]),
         "leo_amd_set_stream": (None, [vp]),
@@ -208,6 +213,47 @@ def leo_amd_update_slice(buffer_bytes, byte_offset, slice_bytes, original_count,
                                                   recovery_count, changed_count, ci, dd, rd))
 
 
+def _opt_ptrs(seq):
+    return None if seq is None else _ptrs(seq)
+
+
+def leo_amd_repair(buffer_bytes, original_count, recovery_count, work_count, original_data, recovery_data,
+                   work_data, recovery_out) -> LeopardResult:
+    """Lost originals into work_data[i], lost recovery pieces with a non-NULL recovery_out[j] into it
+    (include/leopard_amd.h).  Arrays are sequences of addresses (None: a NULL entry) or None for a NULL array."""
+    return LeopardResult(lib.leo_amd_repair(buffer_bytes, original_count, recovery_count, work_count,
+                                            _opt_ptrs(original_data), _opt_ptrs(recovery_data), _opt_ptrs(work_data),
+                                            _opt_ptrs(recovery_out)))
+
+
+def leo_amd_repair_slice(buffer_bytes, byte_offset, slice_bytes, original_count, recovery_count, work_count,
+                         original_data, recovery_data, work_data, recovery_out) -> LeopardResult:
+    return LeopardResult(lib.leo_amd_repair_slice(buffer_bytes, byte_offset, slice_bytes, original_count,
+                                                  recovery_count, work_count, _opt_ptrs(original_data),
+                                                  _opt_ptrs(recovery_data), _opt_ptrs(work_data),
+                                                  _opt_ptrs(recovery_out)))
+
+
+def leo_amd_repair_batch(buffer_bytes, original_count, recovery_count, work_count, original_data, recovery_data,
+                         work_data, recovery_out) -> LeopardResult:
+    """One pointer sequence per object in each list; an entry None is that object's NULL array."""
+    count = _batch_lists(original_data=original_data, recovery_data=recovery_data, work_data=work_data,
+                         recovery_out=recovery_out)
+
+    def arrays(seqs):
+        arrs = [_opt_ptrs(q) for q in seqs]
+        outer = (ctypes.POINTER(ctypes.c_void_p) * max(len(arrs), 1))()
+        for k, a in enumerate(arrs):
+            if a is not None:
+                outer[k] = ctypes.cast(a, ctypes.POINTER(ctypes.c_void_p))
+        outer.keep = arrs
+        return outer
+
+    return LeopardResult(lib.leo_amd_repair_batch(count, buffer_bytes, original_count, recovery_count, work_count,
+                                                  arrays(original_data), arrays(recovery_data), arrays(work_data),
+                                                  arrays(recovery_out)))
+
+
 def register_host(ptr: int, nbytes: int) -> LeopardResult:
     """Pin + map a caller-owned host range (include/leopard_amd.h)."""
     return LeopardResult(lib.leo_amd_register_host(ctypes.c_void_p(ptr), nbytes))
@@ -313,3 +359,40 @@ def update(recovery, original_count: int, indices, deltas):
                          [recovery[j].data_ptr() for j in range(r)])
     _check(res, "leo_amd_update")
     return recovery
+
+
+def repair(original, recovery, lost_originals, lost_recovery, want_recovery=None):
+    """Rebuild: original [K, B] / recovery [R, B] uint8 tensors of one kind (device
+    or host, rows contiguous); the indices listed as lost are passed as NULL.
+    want_recovery: the lost recovery indices to rebuild (default: all of them).
+    Returns ({i: tensor}, {j: tensor}): the rebuilt originals and recovery pieces."""
+    import torch
+    if original.dim() != 2 or recovery.dim() != 2 or original.shape[1] != recovery.shape[1]:
+        raise ValueError(f"original {tuple(original.shape)} and recovery {tuple(recovery.shape)} are not "
+                         "[K, B] and [R, B] of one piece size")
+    if original.stride(1) != 1 or recovery.stride(1) != 1:
+        raise ValueError("pieces must be contiguous rows")
+    if original.device != recovery.device:
+        raise ValueError("original and recovery must be of one kind (same device)")
+    k, nbytes = original.shape
+    r = recovery.shape[0]
+    lo, lr = sorted({int(i) for i in lost_originals}), sorted({int(j) for j in lost_recovery})
+    want = lr if want_recovery is None else sorted({int(j) for j in want_recovery})
+    if any(i < 0 or i >= k for i in lo) or any(j < 0 or j >= r for j in lr):
+        raise ValueError("a lost index is out of range")
+    if not set(want) <= set(lr):
+        raise ValueError("want_recovery must be a subset of lost_recovery")
+    wc = leo_decode_work_count(k, r)
+    out_o = torch.empty((len(lo), nbytes), dtype=torch.uint8, device=original.device)
+    out_r = torch.empty((len(want), nbytes), dtype=torch.uint8, device=original.device)
+    work = [None] * wc
+    for n, i in enumerate(lo):
+        work[i] = out_o[n].data_ptr()
+    rout = [None] * r
+    for n, j in enumerate(want):
+        rout[j] = out_r[n].data_ptr()
+    los, lrs = set(lo), set(lr)
+    res = leo_amd_repair(nbytes, k, r, wc, [None if i in los else original[i].data_ptr() for i in range(k)],
+                         [None if j in lrs else recovery[j].data_ptr() for j in range(r)], work, rout)
+    _check(res, "leo_amd_repair")
+    return {i: out_o[n] for n, i in enumerate(lo)}, {j: out_r[n] for n, j in enumerate(want)}

@@ -87,6 +87,7 @@ struct DeviceTables {
     uint32_t* walsh16 = nullptr;
     uint32_t* qlog16 = nullptr;  // high part of the small FF16 decoder (gf_tables.h: build_high_q16)
     uint8_t* zeros = nullptr;   // zero page
+    uint8_t* sink = nullptr;    // kSinkBytes that kernels may write and nothing reads (composed repairs)
     hipStream_t svc = nullptr;  // library-owned stream for releasing workspace memory
     // Library-owned stream-ordered memory pool of the workspaces: trimming it
     // (release_device_memory) never touches the application's own cached
@@ -118,6 +119,11 @@ struct MatCache {
     size_t bytes = 0;
 };
 constexpr size_t kMatCacheBytes = 64ull << 20;
+// The sink row of a device: where a composed repair sends the encoder's
+// unrequested outputs of pieces up to this size, all of them to the one row
+// (they are never read).  Device-lifetime memory, so a call that uses it holds
+// no workspace memory and needs no completion marker behind its kernels.
+constexpr size_t kSinkBytes = 1ull << 20;
 
 // Bytes of freed stream-ordered memory the library's pool keeps per device.
 constexpr uint64_t kPoolKeepBytes = 256ull << 20;
@@ -159,6 +165,7 @@ LeopardResult ensure_device(int dev, DeviceTables** out) {
         HIP_OK(upload(&d.qlog16, g_h_qlog16), "upload FF16 high-part table");
         HIP_OK(hipMalloc(reinterpret_cast<void**>(&d.zeros), 4096), "zero page");
         HIP_OK(hipMemset(d.zeros, 0, 4096), "zero page");
+        HIP_OK(hipMalloc(reinterpret_cast<void**>(&d.sink), kSinkBytes), "sink row");
         HIP_OK(hipStreamCreateWithFlags(&d.svc, hipStreamNonBlocking), "service stream");
         int cus = 0;
         HIP_OK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev), "compute unit count");
@@ -371,7 +378,9 @@ struct Workspace {
             if (sl.done) (void)hipEventDestroy(sl.done);
             sl = StageSlot{};
         }
-        release_device_memory(dev, {dbuf, ring_dev, direct, el8, bsq});
+        release_device_memory(dev, {dbuf, ring_dev, direct, el8, bsq, rows});
+        rows = nullptr;
+        rows_size = 0;
         if (el8_host) (void)hipHostFree(el8_host);
         el8_host = nullptr;
         for (int e = 0; e < kEl8Events; ++e) {
@@ -607,6 +616,21 @@ struct Workspace {
         direct_size = 0;
         HIP_OK(pool_alloc(reinterpret_cast<void**>(&direct), bytes, dev, stream), "allocate direct rows");
         direct_size = bytes;
+        return Leopard_Success;
+    }
+    // Scratch rows of a composed repair (the encoder's unrequested outputs),
+    // stream-ordered like the arena and apart from it: the encoder's own
+    // reservations may replace the arena while the rows are in use.
+    uint8_t* rows = nullptr;
+    size_t rows_size = 0;
+    LeopardResult reserve_rows(size_t bytes) {
+        touched = true;
+        if (bytes <= rows_size) return Leopard_Success;
+        if (rows) HIP_OK(hipFreeAsync(rows, stream), "free scratch rows");
+        rows = nullptr;
+        rows_size = 0;
+        HIP_OK(pool_alloc(reinterpret_cast<void**>(&rows), bytes, dev, stream), "allocate scratch rows");
+        rows_size = bytes;
         return Leopard_Success;
     }
     // Copies `bytes` from host memory src (or, with src == nullptr, lets
@@ -897,7 +921,7 @@ LeopardResult dense_single_bs(Call& c, uint64_t bytes, uint64_t off, unsigned m,
     return Leopard_Success;
 }
 LeopardResult decode_matrix(Call& c, uint64_t bytes, uint64_t off, unsigned K, unsigned R, const void* const* orig,
-                            const void* const* rec, void** work, bool* done);
+                            const void* const* rec, void** work, bool* done, void* const* rout = nullptr);
 
 // GF(2^8) encoder argument block of one object: columns [off, off + bytes)
 // of every piece (bytes <= kFf8MaxLaunchBytes).
@@ -1069,31 +1093,54 @@ void erasures8(unsigned K, unsigned R, unsigned m, const void* const* orig, cons
         if (!orig[i]) set(m + i);
 }
 
+// Repair: bitmap over recovery indices j < R of the lost pieces the caller wants
+// rebuilt (rec[j] == null and rout[j] != null); false when there is none.
+bool requested8(unsigned R, const void* const* rec, void* const* rout, uint32_t* req) {
+    std::memset(req, 0, 8 * sizeof(uint32_t));
+    bool any = false;
+    for (unsigned j = 0; rout && j < R; ++j)
+        if (!rec[j] && rout[j]) {
+            req[j >> 5] |= 1u << (j & 31);
+            any = true;
+        }
+    return any;
+}
+
 // GF(2^8) decoder argument block of one object (columns [off, off + bytes));
 // returns the decoder kind (kDec8*): with n = 2m, the half-position decoder
 // when no original survives (every received piece in the low half of the
 // positions, every output in the high half; k_ff8_dec_half), the split decoder
 // when some do (k_ff8_dec_split); otherwise the general n-point decoder.
+// Repair (rout != null): a lost recovery piece j with rout[j] != null is an
+// output as well -- its position carries rout[j] and is marked in `needed`;
+// any such piece selects the general decoder, the only one that reveals the
+// low positions.
 int fill_dec8(Ff8DecArgs& a, const DeviceTables* t, unsigned K, unsigned R, const void* const* orig,
-              const void* const* rec, void** work, uint64_t off, uint64_t bytes, const uint32_t* el) {
+              const void* const* rec, void** work, uint64_t off, uint64_t bytes, const uint32_t* el,
+              void* const* rout = nullptr) {
     const unsigned m = next_pow2(R);
     const unsigned Tn = log2u(next_pow2(m + K));
     std::memset(&a, 0, sizeof(a));
-    uint32_t erased[8];
+    uint32_t erased[8], req[8];
     erasures8(K, R, m, orig, rec, erased);
+    const bool any_req = requested8(R, rec, rout, req);
     auto addr = [&](const void* p) { return uint64_t(reinterpret_cast<uintptr_t>(p)) + off; };
-    for (unsigned i = 0; i < R; ++i)
+    for (unsigned i = 0; i < R; ++i) {
         if (rec[i]) a.ptr[i] = addr(rec[i]);
+        else if ((req[i >> 5] >> (i & 31)) & 1u) a.ptr[i] = addr(rout[i]);
+    }
     for (unsigned i = 0; i < K; ++i) a.ptr[m + i] = addr(orig[i] ? orig[i] : work[i]);  // lost: its slot carries the output
     // The pyramids depend only on (K, R, erasure pattern); the last pattern is
     // cached per thread (repeated patterns are the common case).
     struct PyrCache {
         unsigned K = 0, R = 0;
         uint32_t erased[8] = {~0u};
+        uint32_t req[8] = {};
         uint32_t present[kPyr8Words], needed[kPyr8Words];
     };
     thread_local PyrCache pc;
-    if (pc.K != K || pc.R != R || std::memcmp(pc.erased, erased, sizeof(pc.erased)) != 0) {
+    if (pc.K != K || pc.R != R || std::memcmp(pc.erased, erased, sizeof(pc.erased)) != 0 ||
+        std::memcmp(pc.req, req, sizeof(pc.req)) != 0) {
         auto mark = [](uint32_t* pyr, unsigned p) {
             for (unsigned L = 0; L <= 8; ++L) {
                 const unsigned j = p >> L;
@@ -1105,9 +1152,12 @@ int fill_dec8(Ff8DecArgs& a, const DeviceTables* t, unsigned K, unsigned R, cons
         for (unsigned i = 0; i < R; ++i)
             if (rec[i]) mark(pc.present, i);
         for (unsigned i = 0; i < K; ++i) mark(orig[i] ? pc.present : pc.needed, m + i);
+        for (unsigned i = 0; i < R; ++i)
+            if ((req[i >> 5] >> (i & 31)) & 1u) mark(pc.needed, i);
         pc.K = K;
         pc.R = R;
         std::memcpy(pc.erased, erased, sizeof(pc.erased));
+        std::memcpy(pc.req, req, sizeof(pc.req));
     }
     std::memcpy(a.present, pc.present, sizeof(a.present));
     std::memcpy(a.needed, pc.needed, sizeof(a.needed));
@@ -1118,6 +1168,7 @@ int fill_dec8(Ff8DecArgs& a, const DeviceTables* t, unsigned K, unsigned R, cons
     a.R = R;
     a.m = m;
     a.nunits = uint32_t(bytes / 4);
+    if (any_req) return kDec8General;
     bool any_orig = false;
     for (unsigned i = 0; i < K; ++i) any_orig |= orig[i] != nullptr;
     const bool two_halves = Tn >= 2 && 2 * m == (1u << Tn);
@@ -1182,10 +1233,11 @@ void fill_dec8_full(Ff8EncArgs& a, const DeviceTables* t, unsigned m, const void
     a.nunits = uint32_t(bytes / 4);
 }
 
+// rout (repair): outputs of the lost recovery pieces to rebuild as well, or null.
 LeopardResult decode_device8(Call& c, uint64_t bytes, uint64_t off, unsigned K, unsigned R, const void* const* orig,
-                             const void* const* rec, void** work) {
+                             const void* const* rec, void** work, void* const* rout = nullptr) {
     const unsigned Tn = log2u(next_pow2(next_pow2(R) + K));
-    if (full_loss_square(K, R, orig, rec)) {
+    if (full_loss_square(K, R, orig, rec)) {  // (every recovery piece received: nothing to rebuild among them)
         bool done = false;
         LeopardResult r = dense_single_bs(c, bytes, off, R, rec, work, kFormDenseDec, &done);
         if (r != Leopard_Success || done) return r;
@@ -1200,9 +1252,10 @@ LeopardResult decode_device8(Call& c, uint64_t bytes, uint64_t off, unsigned K, 
         unsigned L = 0, N = 0;
         for (unsigned i = 0; i < R; ++i) N += rec[i] != nullptr;
         for (unsigned i = 0; i < K; ++i) (orig[i] ? N : L) += 1;
+        for (unsigned i = 0; rout && i < R; ++i) L += !rec[i] && rout[i];  // repair: both kinds of output
         if (use_matrix(L, N, bytes, true, true)) {
             bool done = false;
-            const LeopardResult r = decode_matrix(c, bytes, off, K, R, orig, rec, work, &done);
+            const LeopardResult r = decode_matrix(c, bytes, off, K, R, orig, rec, work, &done, rout);
             if (r != Leopard_Success || done) return r;
         }
     }
@@ -1230,7 +1283,7 @@ LeopardResult decode_device8(Call& c, uint64_t bytes, uint64_t off, unsigned K, 
     Ff8DecArgs a;
     for (uint64_t pos = 0; pos < bytes; pos += kFf8MaxLaunchBytes) {  // see encode_device
         const int mode =
-            fill_dec8(a, c.t, K, R, orig, rec, work, off + pos, std::min(kFf8MaxLaunchBytes, bytes - pos), el);
+            fill_dec8(a, c.t, K, R, orig, rec, work, off + pos, std::min(kFf8MaxLaunchBytes, bytes - pos), el, rout);
         if (by_value) {
             std::memcpy(a.el_val, elv, sizeof(elv));
             a.el_by_value = 1;
@@ -1331,10 +1384,17 @@ LeopardResult encode_matrix(Call& c, uint64_t bytes, uint64_t off, unsigned K, u
 // Decode of one erasure pattern: lost original i = XOR_j D[i][j] * received j,
 // over every received piece (recovery pieces in index order, then originals):
 // the transform decoder's own map (rs_ff8.hip kernels on unit pieces), also on
-// inputs that are not codewords.
+// inputs that are not codewords.  Repair (rout with a requested piece): the
+// outputs are the lost originals, then the requested recovery pieces, and the
+// key {2, K, R, erased, requested}; the generator runs the repair route of the
+// general decoder on the unit pieces.
 LeopardResult decode_matrix(Call& c, uint64_t bytes, uint64_t off, unsigned K, unsigned R, const void* const* orig,
-                            const void* const* rec, void** work, bool* done) {
+                            const void* const* rec, void** work, bool* done, void* const* rout) {
     *done = false;
+    uint32_t erased[8], req[8];
+    erasures8(K, R, next_pow2(R), orig, rec, erased);
+    const bool any_req = requested8(R, rec, rout, req);
+    auto wanted = [&](unsigned j) { return ((req[j >> 5] >> (j & 31)) & 1u) != 0; };
     std::vector<uint64_t> in, out;
     for (unsigned i = 0; i < R; ++i)
         if (rec[i]) in.push_back(uint64_t(reinterpret_cast<uintptr_t>(rec[i])));
@@ -1342,16 +1402,17 @@ LeopardResult decode_matrix(Call& c, uint64_t bytes, uint64_t off, unsigned K, u
         if (orig[i]) in.push_back(uint64_t(reinterpret_cast<uintptr_t>(orig[i])));
         else out.push_back(uint64_t(reinterpret_cast<uintptr_t>(work[i])));
     }
+    for (unsigned j = 0; j < R; ++j)
+        if (wanted(j)) out.push_back(uint64_t(reinterpret_cast<uintptr_t>(rout[j])));
     const unsigned N = unsigned(in.size()), L = unsigned(out.size());
-    uint32_t erased[8];
-    erasures8(K, R, next_pow2(R), orig, rec, erased);
-    std::vector<uint32_t> key{1u, K, R};
+    std::vector<uint32_t> key{any_req ? 2u : 1u, K, R};
     key.insert(key.end(), erased, erased + 8);
+    if (any_req) key.insert(key.end(), req, req + 8);
     const MatEntry* e = nullptr;
     LeopardResult r = mat_entry(c, std::move(key), L, N,
                                 [&](uint8_t* units, uint8_t* rows, unsigned pitch) {
                                     std::vector<const void*> ou(K), ru(R);
-                                    std::vector<void*> wu(K);
+                                    std::vector<void*> wu(K), qu(R, nullptr);
                                     unsigned j = 0, l = 0;
                                     for (unsigned i = 0; i < R; ++i)
                                         ru[i] = rec[i] ? units + size_t(j++) * pitch : nullptr;
@@ -1359,7 +1420,10 @@ LeopardResult decode_matrix(Call& c, uint64_t bytes, uint64_t off, unsigned K, u
                                         ou[i] = orig[i] ? units + size_t(j++) * pitch : nullptr;
                                         wu[i] = orig[i] ? nullptr : rows + size_t(l++) * pitch;
                                     }
-                                    return decode_device8(c, pitch, 0, K, R, ou.data(), ru.data(), wu.data());
+                                    for (unsigned i = 0; i < R; ++i)
+                                        if (wanted(i)) qu[i] = rows + size_t(l++) * pitch;
+                                    return decode_device8(c, pitch, 0, K, R, ou.data(), ru.data(), wu.data(),
+                                                          any_req ? qu.data() : nullptr);
                                 },
                                 &e);
     if (r != Leopard_Success || !e) return r;
@@ -1380,12 +1444,18 @@ constexpr size_t kDec16OffEl = kDec16OffTmp + 65536 * 4;
 constexpr size_t kDec16OffSl = kDec16OffEl + 65536 * 4;
 constexpr size_t kDec16OffRl = kDec16OffSl + 65536 * 4;
 constexpr size_t kDec16Bytes = kDec16OffRl + 65536 * 4;
+// Repair (rout with a requested piece): the lost recovery pieces j with
+// rout[j] != null are marked in the needed pyramid and get their reveal log
+// values; the requested set is part of the slot's key (a second bitmap), so a
+// leo_decode of the same erasure pattern keeps a state of its own.
 LeopardResult dec16_state(Call& c, unsigned K, unsigned R, const void* const* orig, const void* const* rec,
-                          DecArgs& a) {
+                          DecArgs& a, void* const* rout = nullptr) {
     const unsigned m = next_pow2(R);
     const unsigned n = next_pow2(m + K);
+    bool repair = false;
+    for (unsigned j = 0; rout && j < R && !repair; ++j) repair = !rec[j] && rout[j];
     // error_locations[] = 1 at lost recoveries, [R, m), lost originals (LeopardFF8.cpp:1825-1840)
-    std::vector<uint32_t> key(2 + kDec16Bitmap, 0);
+    std::vector<uint32_t> key(2 + kDec16Bitmap * (repair ? 2 : 1), 0);
     key[0] = K;
     key[1] = R;
     uint32_t* erased = key.data() + 2;
@@ -1395,8 +1465,11 @@ LeopardResult dec16_state(Call& c, unsigned K, unsigned R, const void* const* or
     for (unsigned i = R; i < m; ++i) set(i);
     for (unsigned i = 0; i < K; ++i)
         if (!orig[i]) set(m + i);
+    for (unsigned j = 0; repair && j < R; ++j)
+        if (!rec[j] && rout[j]) key[2 + kDec16Bitmap + (j >> 5)] |= 1u << (j & 31);
     const unsigned words = (std::max(n, 256u) + 31) / 32;
     std::vector<uint32_t> bitmap(erased, erased + words);
+    const std::vector<uint32_t> key_kept = key;  // dec16_slot takes `key`
     Workspace& ws = *c.ws;
     unsigned si = 0;
     bool fresh = false;
@@ -1419,18 +1492,18 @@ LeopardResult dec16_state(Call& c, unsigned K, unsigned R, const void* const* or
             for (unsigned i = 0; i < R; ++i)
                 if (rec[i]) mark(pp, i);
             for (unsigned i = 0; i < K; ++i) mark(orig[i] ? pp : pn, m + i);
+            for (unsigned j = 0; repair && j < R; ++j)
+                if (!rec[j] && rout[j]) mark(pn, j);
         });
         if (r != Leopard_Success) return r;
         HIP_OK(launch_error_locator16(reinterpret_cast<uint32_t*>(st), c.t->walsh16,
                                       reinterpret_cast<uint32_t*>(st + kDec16OffTmp),
                                       reinterpret_cast<uint32_t*>(st + kDec16OffEl),
                                       reinterpret_cast<uint32_t*>(st + kDec16OffSl),
-                                      reinterpret_cast<uint32_t*>(st + kDec16OffRl), m, K, R, c.s),
+                                      reinterpret_cast<uint32_t*>(st + kDec16OffRl), m, K, R, c.s,
+                                      repair ? reinterpret_cast<uint32_t*>(st + kDec16OffPyr) + kPyrWords : nullptr),
                "error locator");
-        ws.dec16[si].key.assign(2 + kDec16Bitmap, 0);
-        ws.dec16[si].key[0] = K;
-        ws.dec16[si].key[1] = R;
-        std::copy(bitmap.begin(), bitmap.end(), ws.dec16[si].key.begin() + 2);
+        ws.dec16[si].key = key_kept;
     }
     a.sktab = c.t->sktab16;
     a.tabs = c.t->tab16;
@@ -1449,13 +1522,17 @@ LeopardResult dec16_state(Call& c, unsigned K, unsigned R, const void* const* or
     return Leopard_Success;
 }
 
+// rout (repair): outputs of the lost recovery pieces to rebuild as well, or
+// null.  With a requested piece the GF(2^16) call takes the three-pass decoder
+// at every n (its passes cover every position; the half-position pass 2 and the
+// narrow-strip decoders write the originals' tiles only).
 LeopardResult decode_device(Call& c, uint64_t bytes, uint64_t off, unsigned K, unsigned R, const void* const* orig,
-                            const void* const* rec, void** work) {
+                            const void* const* rec, void** work, void* const* rout = nullptr) {
     const unsigned m = next_pow2(R);
     const unsigned n = next_pow2(m + K);
     const bool ff16 = n > 256;
     const unsigned Tn = log2u(n);
-    if (!ff16) return decode_device8(c, bytes, off, K, R, orig, rec, work);
+    if (!ff16) return decode_device8(c, bytes, off, K, R, orig, rec, work, rout);
 
     DecArgs a;
     std::memset(&a, 0, sizeof(a));
@@ -1463,12 +1540,20 @@ LeopardResult decode_device(Call& c, uint64_t bytes, uint64_t off, unsigned K, u
     mb.build(a.orig, orig, K, off);
     mb.build(a.rec, rec, R, off);
     mb.build(a.out, work, K, off);
+    std::vector<const void*> wanted;  // rout of the lost pieces only
+    for (unsigned j = 0; rout && j < R; ++j)
+        if (!rec[j] && rout[j]) {
+            wanted.resize(R, nullptr);
+            wanted[j] = rout[j];
+        }
+    const bool repair = !wanted.empty();
+    if (repair) mb.build(a.rec_out, wanted.data(), R, off);
     Workspace& ws = *c.ws;
 
     // Narrow columns and n <= 2048: the two-pass narrow-strip decoder
     // (rs_ff16_small.hip), whose only intermediate is U (tiles with received data).
     const unsigned ntiles_in = (m + K + (1u << kLoBits) - 1) >> kLoBits;
-    const bool narrow = g_q16_ok && decode16_small_supported(Tn) && bytes <= kNarrowColumnsMax;
+    const bool narrow = !repair && g_q16_ok && decode16_small_supported(Tn) && bytes <= kNarrowColumnsMax;
     // few output tiles and pieces of at least kOnePassMinBytes (60 KiB: below
     // that the one-pass grid leaves SIMDs idle and measured slower, 32 KiB
     // 96.7 vs 87.2 us, rs_ff16_small.hip): the one-pass form (no U slab);
@@ -1484,13 +1569,13 @@ LeopardResult decode_device(Call& c, uint64_t bytes, uint64_t off, unsigned K, u
     r = mb.flush(ws, reinterpret_cast<uint64_t*>(ws.dbuf), c.s);  // piece tables (if any)
     if (r != Leopard_Success) return r;
     ++ws.dec16_call;
-    if ((r = dec16_state(c, K, R, orig, rec, a)) != Leopard_Success) return r;
+    if ((r = dec16_state(c, K, R, orig, rec, a, repair ? rout : nullptr)) != Leopard_Success) return r;
     a.nlo = (m + K + (1u << kLoBits) - 1) >> kLoBits;
     // No original survives and n = 2m: the received pieces fill only the low half
     // (k_dec_hi_half); pass 1 then runs the recovery tiles only.
     bool any_orig = false;
     for (unsigned i = 0; i < K; ++i) any_orig |= orig[i] != nullptr;
-    const bool half = !any_orig && Tn >= kLoBits + 2 && 2 * m == n && ff8_half_decoder_enabled();
+    const bool half = !repair && !any_orig && Tn >= kLoBits + 2 && 2 * m == n && ff8_half_decoder_enabled();
     if (half) {
         a.nlo = (R + (1u << kLoBits) - 1) >> kLoBits;
         a.fused = c.t->fused16 + fused16_base(Tn - 1);
@@ -1527,7 +1612,8 @@ LeopardResult decode_device(Call& c, uint64_t bytes, uint64_t off, unsigned K, u
         HIP_OK(half ? launch_decode_hi_half(b, c.s) : launch_decode_hi(b, c.s), "decode pass 2");
         b.a_in = PieceMap{nullptr, A, slice, 0};
         b.b_in = PieceMap{nullptr, Uu, slice, 0};
-        HIP_OK(launch_decode_fin(b, c.s), "decode pass 3");
+        b.rec_out.off = off + pos;
+        HIP_OK(launch_decode_fin(b, c.s, repair), "decode pass 3");
     }
     return Leopard_Success;
 }
@@ -3012,6 +3098,397 @@ LeopardResult decode_batch(unsigned count, uint64_t bytes, unsigned K, unsigned 
     return Leopard_Success;
 }
 
+// --------------------------------------------------------------- repair ----
+// leo_amd_repair: lost originals into work_data, lost and requested recovery
+// pieces into recovery_out, in the decode pass (decode_device with rout): the
+// general GF(2^8) decoder or the matrix path, the three-pass GF(2^16) decoder.
+// A call that requests no recovery piece is the decoder's own routes with
+// nothing copied for received originals.
+
+// LEO_AMD_REPAIR_COMPOSE=1 forces the composition (repair_compose); read once.
+bool repair_compose_forced() {
+    static const bool v = [] {
+        const char* e = std::getenv("LEO_AMD_REPAIR_COMPOSE");
+        return e && e[0] == '1';
+    }();
+    return v;
+}
+
+// LEO_AMD_REPAIR_COMPOSE=0 keeps every call on the fused routes (experiment
+// builds only, for the A/B of the rules below); read once.
+bool repair_fused_forced() {
+    static const bool v = experiment_off("LEO_AMD_REPAIR_COMPOSE");
+    return v;
+}
+
+struct RepairCounts {
+    unsigned lost = 0, lost_i = 0, got = 0, got_i = 0, wanted = 0;
+};
+RepairCounts repair_counts(unsigned K, unsigned R, const void* const* orig, const void* const* rec, void* const* rout) {
+    RepairCounts n;
+    for (unsigned i = 0; i < K; ++i)
+        if (!orig[i]) { ++n.lost; n.lost_i = i; }
+    for (unsigned j = 0; j < R; ++j) {
+        if (rec[j]) { ++n.got; n.got_i = j; }
+        else if (rout[j]) ++n.wanted;
+    }
+    return n;
+}
+
+// The composition the fused routes replace: the decoder for the lost
+// originals, then the encoder over received and rebuilt originals, requested
+// rows written to the caller and the others to scratch: the device's sink row
+// for pieces up to kSinkBytes, rows of the workspace above that.
+LeopardResult repair_compose(Call& c, uint64_t bytes, uint64_t off, unsigned K, unsigned R, const void* const* orig,
+                             const void* const* rec, void** work, void* const* rout, const RepairCounts& n) {
+    LeopardResult r = Leopard_Success;
+    if (n.lost > 0 && (r = decode_device(c, bytes, off, K, R, orig, rec, work)) != Leopard_Success) return r;
+    std::vector<const void*> full(K);
+    for (unsigned i = 0; i < K; ++i) full[i] = orig[i] ? orig[i] : work[i];
+    Workspace& ws = *c.ws;
+    const bool sink = bytes <= kSinkBytes;  // else rows of their own in the workspace
+    if (!sink && (r = ws.reserve_rows(size_t(R - n.wanted) * bytes)) != Leopard_Success) return r;
+    std::vector<void*> w(R);
+    unsigned row = 0;
+    for (unsigned j = 0; j < R; ++j)  // the encoder adds `off` to every piece
+        w[j] = !rec[j] && rout[j] ? rout[j]
+               : sink             ? static_cast<void*>(c.t->sink - off)
+                                  : static_cast<void*>(ws.rows + size_t(row++) * bytes - off);
+    r = encode_device(c, bytes, off, K, R, full.data(), w.data());
+    if (!sink && ws.rows_size > kDirectKeepBytes) {  // large rows do not stay with the thread
+        (void)hipFreeAsync(ws.rows, c.s);
+        ws.rows = nullptr;
+        ws.rows_size = 0;
+    }
+    return r;
+}
+
+// Where a single call takes the composition by default (measured, DESIGN.md
+// section 7.10):
+//  - no original lost: the fused route would run the whole decoder transform
+//    for what the encoder alone computes (128+128 x 64 KiB, 64 recovery pieces
+//    lost: 17.1 us fused, 8.7 composed; 1000+200 x 64 KiB, 100 lost: 130.6, 58.2);
+//  - GF(2^16) with n <= 2048 on pieces under kRepairFusedMinBytes16: the
+//    narrow-strip decoder and encoder (rs_ff16_small.hip) fill the GPU with
+//    128-byte strips where the three passes run 512-byte tiles (1000+200,
+//    100 + 100 lost, fused / composed: 2560 B 62.8 / 47.5 us, 8 KiB 72.0 /
+//    67.5, 16 KiB 82.4 / 91.0, 32 KiB 123.6 / 129.9, 64 KiB 182.3 / 210.8).
+constexpr uint64_t kRepairFusedMinBytes16 = 16ull << 10;
+bool repair_composes(unsigned K, unsigned R, uint64_t bytes, const RepairCounts& n) {
+    if (repair_compose_forced()) return true;
+    if (repair_fused_forced()) return false;
+    if (n.lost == 0) return true;
+    return narrow_decode16(K, R, bytes) && bytes < kRepairFusedMinBytes16;
+}
+// Device-resident GF(2^8) batches (measured): with
+// n = 2m the split decoder and the dense encoder tile, one batch launch each,
+// beat the general n-point tile once the batch fills the GPU (128+128 x 64 KiB,
+// 32 + 32 lost, fused / composed: 4 objects 73.4 / 82.4 us, 16 objects 277.6 /
+// 269.5, 64 objects 1014.5 / 884.8): from kRepairBatchStripsPerCu 256-byte
+// strips per compute unit.  With n != 2m the general tile is the decoder's own
+// and the batch stays fused (64 objects of 100+10 x 64 KiB: 329 / 446).
+constexpr uint64_t kRepairBatchStripsPerCu = 16;
+bool repair_batch_composes(unsigned K, unsigned R, uint64_t bytes, size_t objects, unsigned cus) {
+    const unsigned m = next_pow2(R);
+    if (next_pow2(m + K) != 2 * m || repair_fused_forced()) return false;
+    return objects * ((bytes + 255) / 256) >= kRepairBatchStripsPerCu * cus;
+}
+
+// Device-visible pieces, columns [off, off + bytes), something to do, K > 1.
+LeopardResult repair_device(Call& c, uint64_t bytes, uint64_t off, unsigned K, unsigned R, const void* const* orig,
+                            const void* const* rec, void** work, void* const* rout, const RepairCounts& n) {
+    if (R == 1) {  // one parity piece: the XOR of the others (leopard.cpp:152-160, 294-303)
+        std::vector<const void*> src;
+        if (rec[0]) src.push_back(rec[0]);
+        for (unsigned i = 0; i < K; ++i)
+            if (orig[i]) src.push_back(orig[i]);
+        return xor_device(c, bytes, off, src.data(), unsigned(src.size()), n.lost ? work[n.lost_i] : rout[0]);
+    }
+    if (n.wanted == 0) return decode_device(c, bytes, off, K, R, orig, rec, work);
+    if (repair_composes(K, R, bytes, n)) return repair_compose(c, bytes, off, K, R, orig, rec, work, rout, n);
+    return decode_device(c, bytes, off, K, R, orig, rec, work, rout);
+}
+
+// Validation of leo_amd_repair, in the header's order up to CallInitialize.
+LeopardResult check_repair(uint64_t bytes, unsigned K, unsigned R, const void* const* orig, const void* const* rec,
+                           void* const* work, void* const* rout) {
+    if (bytes == 0 || bytes % 64 != 0) return Leopard_InvalidSize;
+    if (R == 0 || R > K) return Leopard_InvalidCounts;
+    if (!orig || !rec || !work || !rout) {
+        tls.last_error = std::string(!orig ? "original_data" : !rec ? "recovery_data" : !work ? "work_data" : "recovery_out") +
+                         " is NULL";
+        return Leopard_InvalidInput;
+    }
+    if (!g_initialized) return Leopard_CallInitialize;
+    return Leopard_Success;
+}
+// ... and after it.  *nothing: no piece to write.
+LeopardResult check_repair_work(unsigned K, unsigned R, unsigned work_count, const void* const* orig, void* const* work,
+                                const RepairCounts& n, bool* nothing) {
+    *nothing = false;
+    if (n.got < n.lost) return Leopard_NeedMoreData;
+    if (n.lost == 0 && n.wanted == 0) {
+        *nothing = true;
+        return Leopard_Success;
+    }
+    if (K != 1 && R != 1) {
+        const unsigned nn = next_pow2(next_pow2(R) + K);
+        if (work_count != nn) return Leopard_InvalidCounts;
+        if (nn > 65536) return Leopard_TooMuchData;
+    }
+    for (unsigned i = 0; i < K; ++i)
+        if (!orig[i] && !work[i]) {
+            char buf[96];
+            std::snprintf(buf, sizeof(buf), "work_data[%u] is NULL but original %u is lost", i, i);
+            tls.last_error = buf;
+            return Leopard_InvalidInput;
+        }
+    return Leopard_Success;
+}
+
+// One validated call with something to do.
+LeopardResult repair_any(uint64_t bytes, uint64_t off, unsigned K, unsigned R, const void* const* orig,
+                         const void* const* rec, void** work, void* const* rout) {
+    const RepairCounts n = repair_counts(K, R, orig, rec, rout);
+    const void* first = nullptr;
+    for (unsigned i = 0; i < K && !first; ++i) first = orig[i];
+    for (unsigned i = 0; i < R && !first; ++i) first = rec[i];
+    MemKind kind;
+    const int dev = pick_device(first, &kind);
+    DeviceGuard guard(dev);
+    Call c;
+    LeopardResult r = begin_call(dev, c);
+    if (r != Leopard_Success) return r;
+    // K == 1 (and so R == 1): the two pieces are copies of each other
+    const void* k1_src = K == 1 ? (orig[0] ? orig[0] : rec[n.got_i]) : nullptr;
+    void* k1_dst = K == 1 ? (n.lost ? work[0] : rout[0]) : nullptr;
+
+    if (kind == MemKind::Device) {
+        if (K == 1)
+            HIP_OK(hipMemcpyAsync(static_cast<uint8_t*>(k1_dst) + off, static_cast<const uint8_t*>(k1_src) + off, bytes,
+                                  hipMemcpyDeviceToDevice, c.s),
+                   "copy");
+        else if ((r = repair_device(c, bytes, off, K, R, orig, rec, work, rout, n)) != Leopard_Success)
+            return r;
+        return finish(c, false);
+    }
+    if (K == 1) {
+        parallel_copy({{static_cast<uint8_t*>(k1_dst) + off, static_cast<const uint8_t*>(k1_src) + off, bytes}});
+        return Leopard_Success;
+    }
+    if (!tls.fanout_worker) {  // columns over several GPUs
+        const unsigned nr = fanout_ranges(bytes);
+        if (nr > 1)
+            return fanout(nr, bytes, [&](uint64_t len, uint64_t o) {
+                return repair_any(len, off + o, K, R, orig, rec, work, rout);
+            });
+    }
+    // the pieces the call writes: work of the lost originals, rout of the lost and requested recovery pieces
+    std::vector<const void*> wl(K, nullptr), ql(R, nullptr);
+    for (unsigned i = 0; i < K; ++i)
+        if (!orig[i]) wl[i] = work[i];
+    for (unsigned j = 0; j < R; ++j)
+        if (!rec[j]) ql[j] = rout[j];
+    {  // caller-registered host memory: the kernels run on it in place
+        std::vector<void*> dorig, drec, dwork, dout;
+        if (map_registered(orig, K, off, bytes, dorig) && map_registered(rec, R, off, bytes, drec) &&
+            map_registered(wl.data(), K, off, bytes, dwork) && map_registered(ql.data(), R, off, bytes, dout)) {
+            r = repair_device(c, bytes, off, K, R, const_cast<const void* const*>(dorig.data()),
+                              const_cast<const void* const*>(drec.data()), dwork.data(), dout.data(), n);
+            if (r != Leopard_Success) return r;
+            return finish(c, true);
+        }
+    }
+    // pageable memory staged as dense rows: inputs = received recovery pieces,
+    // then received originals; outputs = lost originals, then requested recovery pieces
+    std::vector<int> in_rec(R, -1), in_orig(K, -1), out_orig(K, -1), out_rec(R, -1);
+    std::vector<const uint8_t*> hin;
+    std::vector<uint8_t*> hout;
+    for (unsigned j = 0; j < R; ++j)
+        if (rec[j]) {
+            in_rec[j] = int(hin.size());
+            hin.push_back(static_cast<const uint8_t*>(rec[j]) + off);
+        }
+    for (unsigned i = 0; i < K; ++i)
+        if (orig[i]) {
+            in_orig[i] = int(hin.size());
+            hin.push_back(static_cast<const uint8_t*>(orig[i]) + off);
+        }
+    for (unsigned i = 0; i < K; ++i)
+        if (wl[i]) {
+            out_orig[i] = int(hout.size());
+            hout.push_back(static_cast<uint8_t*>(work[i]) + off);
+        }
+    for (unsigned j = 0; j < R; ++j)
+        if (ql[j]) {
+            out_rec[j] = int(hout.size());
+            hout.push_back(static_cast<uint8_t*>(rout[j]) + off);
+        }
+    const SliceFn slice_fn = [&](Call& cs, uint64_t len, uint8_t* din, uint8_t* dout, uint64_t stride) {
+        std::vector<const void*> dorig(K, nullptr), drec(R, nullptr);
+        std::vector<void*> dwork(K, nullptr), dq(R, nullptr);
+        for (unsigned j = 0; j < R; ++j) {
+            if (in_rec[j] >= 0) drec[j] = din + in_rec[j] * stride;
+            if (out_rec[j] >= 0) dq[j] = dout + out_rec[j] * stride;
+        }
+        for (unsigned i = 0; i < K; ++i) {
+            if (in_orig[i] >= 0) dorig[i] = din + in_orig[i] * stride;
+            if (out_orig[i] >= 0) dwork[i] = dout + out_orig[i] * stride;
+        }
+        return repair_device(cs, len, 0, K, R, dorig.data(), drec.data(), dwork.data(), dq.data(), n);
+    };
+    r = run_host_pipeline(c, bytes, hin, hout, slice_fn);
+    if (r != Leopard_Success) return r;
+    return finish(c, true);
+}
+
+LeopardResult repair_checked(uint64_t bytes, uint64_t off, unsigned K, unsigned R, unsigned work_count,
+                             const void* const* orig, const void* const* rec, void** work, void* const* rout) {
+    bool nothing = false;
+    const LeopardResult r = check_repair_work(K, R, work_count, orig, work, repair_counts(K, R, orig, rec, rout), &nothing);
+    if (r != Leopard_Success || nothing) return r;
+    return repair_any(bytes, off, K, R, orig, rec, work, rout);
+}
+
+LeopardResult repair_batch(unsigned count, uint64_t bytes, unsigned K, unsigned R, unsigned work_count,
+                           const void* const* const* orig, const void* const* const* rec, void** const* work,
+                           void** const* rout) {
+    if (bytes == 0 || bytes % 64 != 0) return Leopard_InvalidSize;
+    if (R == 0 || R > K) return Leopard_InvalidCounts;
+    if (!orig || !rec || !work || !rout) {
+        tls.last_error = std::string(!orig ? "original_data" : !rec ? "recovery_data" : !work ? "work_data" : "recovery_out") +
+                         " is NULL";
+        return Leopard_InvalidInput;
+    }
+    std::vector<unsigned> todo;  // the objects with something to write
+    std::vector<RepairCounts> counts;
+    bool compose = false;  // some object takes the composition as a single call
+    for (unsigned o = 0; o < count; ++o) {
+        LeopardResult r = check_repair(bytes, K, R, orig[o], rec[o], work[o], rout[o]);
+        if (r != Leopard_Success) return r;
+        const RepairCounts n = repair_counts(K, R, orig[o], rec[o], rout[o]);
+        bool nothing = false;
+        if ((r = check_repair_work(K, R, work_count, orig[o], work[o], n, &nothing)) != Leopard_Success) return r;
+        if (nothing) continue;
+        todo.push_back(o);
+        counts.push_back(n);
+        compose = compose || (n.wanted > 0 && repair_composes(K, R, bytes, n));
+    }
+    if (todo.empty()) return Leopard_Success;
+    bool any_wanted = false;
+    for (const RepairCounts& n : counts) any_wanted = any_wanted || n.wanted > 0;
+    compose = compose || !any_wanted;  // nothing requested: leo_amd_decode_batch's own routes
+    const unsigned m = next_pow2(R), nn = next_pow2(m + K);
+    if (K > 1 && R > 1 && nn <= 256 && bytes <= kFf8MaxLaunchBytes) {
+        // device-resident GF(2^8) objects on one device: one general-decoder
+        // launch per kDecBatchChunk objects, as decode_batch
+        const void* first = nullptr;
+        for (unsigned i = 0; i < K && !first; ++i) first = orig[todo[0]][i];
+        for (unsigned i = 0; i < R && !first; ++i) first = rec[todo[0]][i];
+        MemKind kind = MemKind::Host;
+        const int dev = pick_device(first, &kind);
+        RangeCache rc;
+        bool on_dev = kind == MemKind::Device;
+        for (size_t t = 0; t < todo.size() && on_dev; ++t) {
+            const unsigned o = todo[t];
+            on_dev = rc.all_on(orig[o], K, bytes, dev) && rc.all_on(rec[o], R, bytes, dev);
+            for (unsigned i = 0; i < K && on_dev; ++i)
+                if (!orig[o][i]) on_dev = rc.on(work[o][i], bytes, dev);
+            for (unsigned j = 0; j < R && on_dev; ++j)
+                if (!rec[o][j] && rout[o][j]) on_dev = rc.on(rout[o][j], bytes, dev);
+        }
+        DeviceTables* dt = nullptr;
+        if (on_dev) {
+            const LeopardResult rt = ensure_device(dev, &dt);
+            if (rt != Leopard_Success) return rt;
+        }
+        if (on_dev && (compose || repair_batch_composes(K, R, bytes, todo.size(), dt->cus))) {
+            // the composition as two batches: leo_amd_decode_batch over the
+            // objects that lost originals, leo_amd_encode_batch over the ones
+            // that want recovery pieces (unrequested rows in scratch)
+            std::vector<const void* const*> bo, br;
+            std::vector<void**> bw;
+            for (size_t t = 0; t < todo.size(); ++t)
+                if (counts[t].lost > 0) {
+                    bo.push_back(orig[todo[t]]);
+                    br.push_back(rec[todo[t]]);
+                    bw.push_back(work[todo[t]]);
+                }
+            LeopardResult r = Leopard_Success;
+            if (!bo.empty() && (r = decode_batch(unsigned(bo.size()), bytes, K, R, work_count, bo.data(), br.data(),
+                                                 bw.data())) != Leopard_Success)
+                return r;
+            size_t nrows = 0, nenc = 0;
+            for (const RepairCounts& n : counts)
+                if (n.wanted > 0) nrows += R - n.wanted, ++nenc;
+            if (nenc == 0) return Leopard_Success;
+            const bool sink = bytes <= kSinkBytes;
+            uint8_t* rows = dt->sink;
+            if (!sink) {
+                DeviceGuard guard(dev);
+                Call c;
+                if ((r = begin_call(dev, c)) != Leopard_Success) return r;
+                if ((r = c.ws->reserve_rows(nrows * bytes)) != Leopard_Success) return r;
+                rows = c.ws->rows;  // the encode batch below runs on the same workspace and marks its use
+            }
+            std::vector<std::vector<const void*>> full(nenc, std::vector<const void*>(K));
+            std::vector<std::vector<void*>> w(nenc, std::vector<void*>(2 * m, nullptr));
+            std::vector<const void* const*> fo;
+            std::vector<void**> fw;
+            size_t e = 0, row = 0;
+            for (size_t t = 0; t < todo.size(); ++t) {
+                if (counts[t].wanted == 0) continue;
+                const unsigned o = todo[t];
+                for (unsigned i = 0; i < K; ++i) full[e][i] = orig[o][i] ? orig[o][i] : work[o][i];
+                for (unsigned j = 0; j < R; ++j)
+                    w[e][j] = !rec[o][j] && rout[o][j] ? rout[o][j]
+                                                       : static_cast<void*>(rows + (sink ? 0 : row++) * bytes);
+                fo.push_back(full[e].data());
+                fw.push_back(w[e].data());
+                ++e;
+            }
+            return encode_batch(unsigned(nenc), bytes, K, R, 2 * m, fo.data(), fw.data());
+        }
+        if (on_dev) {
+            const unsigned Tn = log2u(nn);
+            for (size_t t0 = 0; t0 < todo.size(); t0 += kDecBatchChunk) {
+                const unsigned nb = unsigned(std::min<size_t>(kDecBatchChunk, todo.size() - t0));
+                std::vector<const uint32_t*> els(nb);
+                const LeopardResult r = run_batch8<Ff8DecArgs>(
+                    dev, nb,
+                    [&](Ff8DecArgs& a, const DeviceTables* t, unsigned b) {
+                        const unsigned o = todo[t0 + b];
+                        fill_dec8(a, t, K, R, orig[o], rec[o], work[o], 0, bytes, els[b], rout[o]);
+                        return kDec8General;  // the one kind that reveals recovery positions
+                    },
+                    [&](const Ff8DecArgs* d, int, hipStream_t s) {
+                        return launch_ff8_decode_batch(Tn, d, nb, uint32_t(bytes / 4), kDec8General, s);
+                    },
+                    [&](Call& c) -> LeopardResult {  // the error locators of the new patterns, one launch
+                        c.ws->el8_begin();
+                        c.ws->touched = true;  // the batch's kernels read the slots
+                        std::vector<El8Job> jobs;
+                        for (unsigned b = 0; b < nb; ++b) {
+                            const unsigned o = todo[t0 + b];
+                            uint32_t erased[8];
+                            erasures8(K, R, m, orig[o], rec[o], erased);
+                            const LeopardResult re = c.ws->el8_slot(erased, jobs, &els[b]);
+                            if (re != Leopard_Success) return re;
+                        }
+                        return flush_el8(*c.ws, c.t, jobs, c.s);
+                    });
+                if (r != Leopard_Success) return r;
+            }
+            return Leopard_Success;
+        }
+    }
+    for (unsigned o : todo) {
+        const LeopardResult r = repair_any(bytes, 0, K, R, orig[o], rec[o], work[o], rout[o]);
+        if (r != Leopard_Success) return r;
+    }
+    return Leopard_Success;
+}
+
 }  // namespace
 }  // namespace lamd
 
@@ -3167,6 +3644,38 @@ LEO_EXPORT LeopardResult leo_amd_decode_batch(unsigned object_count, uint64_t bu
                                               const void* const* const* recovery_data, void** const* work_data) {
     return decode_batch(object_count, buffer_bytes, original_count, recovery_count, work_count, original_data,
                         recovery_data, work_data);
+}
+
+LEO_EXPORT LeopardResult leo_amd_repair(uint64_t buffer_bytes, unsigned original_count, unsigned recovery_count,
+                                        unsigned work_count, const void* const* original_data,
+                                        const void* const* recovery_data, void** work_data, void** recovery_out) {
+    const LeopardResult r =
+        check_repair(buffer_bytes, original_count, recovery_count, original_data, recovery_data, work_data, recovery_out);
+    if (r != Leopard_Success) return r;
+    return repair_checked(buffer_bytes, 0, original_count, recovery_count, work_count, original_data, recovery_data,
+                          work_data, recovery_out);
+}
+
+LEO_EXPORT LeopardResult leo_amd_repair_slice(uint64_t buffer_bytes, uint64_t byte_offset, uint64_t slice_bytes,
+                                              unsigned original_count, unsigned recovery_count, unsigned work_count,
+                                              const void* const* original_data, const void* const* recovery_data,
+                                              void** work_data, void** recovery_out) {
+    if (slice_bytes == 0 || slice_bytes % 64 || byte_offset % 64 || byte_offset + slice_bytes > buffer_bytes)
+        return Leopard_InvalidSize;
+    const LeopardResult r =
+        check_repair(buffer_bytes, original_count, recovery_count, original_data, recovery_data, work_data, recovery_out);
+    if (r != Leopard_Success) return r;
+    return repair_checked(slice_bytes, byte_offset, original_count, recovery_count, work_count, original_data,
+                          recovery_data, work_data, recovery_out);
+}
+
+LEO_EXPORT LeopardResult leo_amd_repair_batch(unsigned object_count, uint64_t buffer_bytes, unsigned original_count,
+                                              unsigned recovery_count, unsigned work_count,
+                                              const void* const* const* original_data,
+                                              const void* const* const* recovery_data, void** const* work_data,
+                                              void** const* recovery_out) {
+    return repair_batch(object_count, buffer_bytes, original_count, recovery_count, work_count, original_data,
+                        recovery_data, work_data, recovery_out);
 }
 
 LEO_EXPORT LeopardResult leo_amd_register_host(void* ptr, uint64_t bytes) {

@@ -51,6 +51,9 @@ struct DecArgs {
     // build_high_q16), and the tiles holding originals [tile0, tile0 + nout)
     const uint32_t* qlog;
     unsigned tile0, nout;
+    // repair (leo_amd_repair, three-pass decoder only): outputs of the lost,
+    // requested recovery pieces, positions [0, R); needed_pyr marks them too
+    PieceMap rec_out;
 };
 
 // GF(2^8) kernels (codeword length n <= 256).  Everything a launch needs travels
@@ -166,10 +169,13 @@ hipError_t launch_encode_hi(const EncArgs& a, hipStream_t s);
 hipError_t launch_encode_fin(const EncArgs& a, hipStream_t s);
 hipError_t launch_decode_lo(const DecArgs& a, hipStream_t s);
 hipError_t launch_decode_hi(const DecArgs& a, hipStream_t s);
-hipError_t launch_decode_fin(const DecArgs& a, hipStream_t s);
+// repair: lost recovery positions marked in a.needed_pyr are revealed into a.rec_out
+hipError_t launch_decode_fin(const DecArgs& a, hipStream_t s, bool repair = false);
+// requested: level 0 of the needed pyramid when lost recovery positions are to
+// be revealed as well (repair), else null
 hipError_t launch_error_locator16(const uint32_t* erased, const uint32_t* walsh, uint32_t* tmp, uint32_t* el,
                                   uint32_t* scale_logs, uint32_t* reveal_logs, unsigned m, unsigned K, unsigned R,
-                                  hipStream_t s);
+                                  hipStream_t s, const uint32_t* requested = nullptr);
 hipError_t launch_xor_reduce(const XorArgs& a, hipStream_t s);
 // Small GF(2^16) codes on narrow column strips (rs_ff16_small.hip)
 bool encode16_small_supported(unsigned Tm);

@@ -570,7 +570,10 @@ __global__ void __launch_bounds__(threads16(T, R), LAMD_HI_WAVES) k_dec_hi_half(
 // (work[i] = z[m + i] * exp(-el[m + i]), LeopardFF8.cpp:1913-1915; the reveal
 // tables, log value reveal_logs[p], staged in LDS).  U of a low tile without
 // received data is zero and was never written.
-template <int R, int S>
+// kRepair (leo_amd_repair): a lost recovery position p < R that needed_pyr
+// marks is revealed the same way, into a.rec_out (the transform is symmetric in
+// the positions; reveal_logs holds kModulus - el[p] there as well).
+template <int R, int S, bool kRepair = false>
 __global__ void __launch_bounds__(threads16(kLoBits, R), 4) k_dec_fin(DecArgs a) {
     constexpr int T = kLoBits;
     constexpr int NT = threads16(T, R);
@@ -599,11 +602,15 @@ __global__ void __launch_bounds__(threads16(kLoBits, R), 4) k_dec_fin(DecArgs a)
     const unsigned p0 = ps.global(TL::piece(0, 0, w));
     const uint32_t ew = cload(a.erased_dev + (p0 >> 5)) >> (p0 & 31);
     uint8_t* op[TL::NR];
+    uint32_t nw = 0;  // kRepair: level 0 of the needed pyramid, the lane's positions
+    if constexpr (kRepair) nw = cload(a.needed_pyr + pyr_offset(0) + (p0 >> 5)) >> (p0 & 31);
 #pragma unroll
     for (int r = 0; r < TL::NR; ++r) {
         const unsigned p = p0 + unsigned(r);
         op[r] = nullptr;
         if (p >= a.m && p < a.m + a.K && ((ew >> r) & 1u)) op[r] = a.out.ptr(p - a.m) + cl.strip;
+        if constexpr (kRepair)
+            if (p < a.R && ((ew >> r) & 1u) && ((nw >> r) & 1u)) op[r] = a.rec_out.ptr(p) + cl.strip;
     }
 #pragma unroll
     for (int r = 0; r < TL::NR; ++r) asm volatile("" : "+s"(op[r]));
@@ -655,10 +662,13 @@ LDEV void fwht256(unsigned (&e)[4], unsigned lane) {
 // the per-position log values of the decoder's multiplies: scale_logs[p] =
 // el[p] for a received piece (LeopardFF8.cpp:1857-1877), reveal_logs[p] =
 // kModulus - el[p] for a lost original (:1913-1915), the all-zero table
-// (65536) elsewhere.
+// (65536) elsewhere.  kRepair: reveal_logs[p] = kModulus - el[p] also for a
+// lost recovery position p < R whose bit is set in `requested` (level 0 of the
+// needed pyramid).
+template <bool kRepair = false>
 __global__ void __launch_bounds__(64) k_el16_rows(const uint32_t* erased, uint32_t* tmp, uint32_t* el,
                                                  uint32_t* scale_logs, uint32_t* reveal_logs, int mode, unsigned m,
-                                                 unsigned K, unsigned R) {
+                                                 unsigned K, unsigned R, const uint32_t* requested) {
     const unsigned lane = threadIdx.x, row = blockIdx.x;
     unsigned e[4];
 #pragma unroll
@@ -677,7 +687,9 @@ __global__ void __launch_bounds__(64) k_el16_rows(const uint32_t* erased, uint32
             const bool lost = bit_set(erased, p);
             const bool orig = p >= m && p < m + K;
             scale_logs[p] = !lost && (p < R || orig) ? e[j] : 65536u;
-            reveal_logs[p] = lost && orig ? 65535u - e[j] : 65536u;
+            bool reveal = lost && orig;
+            if constexpr (kRepair) reveal = reveal || (lost && p < R && bit_set(requested, p));
+            reveal_logs[p] = reveal ? 65535u - e[j] : 65536u;
         }
     }
 }
@@ -820,17 +832,27 @@ hipError_t launch_decode_hi(const DecArgs& a, hipStream_t s) {
 hipError_t launch_decode_hi_half(const DecArgs& a, hipStream_t s) {
     return dispatch_T<DecHiHalfFn, 1, 7>(a.Tn - 1 - kLoBits, a, s);
 }
-hipError_t launch_decode_fin(const DecArgs& a, hipStream_t s) {
+hipError_t launch_decode_fin(const DecArgs& a, hipStream_t s, bool repair) {
     const unsigned n = 1u << a.Tn;
-    return launch(&k_dec_fin<kLoR, kLoS>, dim3(tiles_for(a.nunits), n >> kLoBits), threads16(kLoBits, kLoR),
+    const dim3 grid(tiles_for(a.nunits), n >> kLoBits);
+    if (repair)
+        return launch(&k_dec_fin<kLoR, kLoS, true>, grid, threads16(kLoBits, kLoR),
+                      lds16_dwords<kLoBits, kLoR, kLoS>(1, 1 << kLoBits), s, &a);
+    return launch(&k_dec_fin<kLoR, kLoS>, grid, threads16(kLoBits, kLoR),
                   lds16_dwords<kLoBits, kLoR, kLoS>(1, 1 << kLoBits), s, &a);
 }
 hipError_t launch_error_locator16(const uint32_t* erased, const uint32_t* walsh, uint32_t* tmp, uint32_t* el,
                                   uint32_t* scale_logs, uint32_t* reveal_logs, unsigned m, unsigned K, unsigned R,
-                                  hipStream_t s) {
-    hipLaunchKernelGGL(k_el16_rows, dim3(256), dim3(64), 0, s, erased, tmp, el, scale_logs, reveal_logs, 0, m, K, R);
+                                  hipStream_t s, const uint32_t* requested) {
+    hipLaunchKernelGGL(k_el16_rows<false>, dim3(256), dim3(64), 0, s, erased, tmp, el, scale_logs, reveal_logs, 0, m,
+                       K, R, requested);
     hipLaunchKernelGGL(k_el16_cols, dim3(256), dim3(64), 0, s, tmp, walsh);
-    hipLaunchKernelGGL(k_el16_rows, dim3(256), dim3(64), 0, s, erased, tmp, el, scale_logs, reveal_logs, 1, m, K, R);
+    if (requested)
+        hipLaunchKernelGGL(k_el16_rows<true>, dim3(256), dim3(64), 0, s, erased, tmp, el, scale_logs, reveal_logs, 1,
+                           m, K, R, requested);
+    else
+        hipLaunchKernelGGL(k_el16_rows<false>, dim3(256), dim3(64), 0, s, erased, tmp, el, scale_logs, reveal_logs, 1,
+                           m, K, R, requested);
     return hipGetLastError();
 }
 hipError_t launch_xor_reduce(const XorArgs& a, hipStream_t s) {
