@@ -199,6 +199,78 @@ LEO_EXPORT LeopardResult leo_amd_repair_batch(
     unsigned work_count, const void* const* const* original_data, const void* const* const* recovery_data,
     void** const* work_data, void** const* recovery_out);
 
+/* Scrub: check that stored recovery pieces still belong to the originals,
+ * without writing any piece.  A store proves periodically that the K originals
+ * and the R recovery pieces it holds still form one codeword; this is
+ * leo_encode into scratch plus a compare, inside one call that keeps the
+ * scratch bounded and reports one bit per recovery piece.
+ *
+ * Every original is needed: original_data[i] == NULL is Leopard_InvalidInput
+ * (leo_amd_last_error() names i).  recovery_data[j] == NULL means "piece j is
+ * not at hand, do not check it".  A checked piece j mismatches when any byte of
+ * recovery_data[j] differs from what leo_encode of these originals writes to
+ * work_data[j] (slice form: any byte of the slice's columns; original_count ==
+ * 1: every piece is compared with the original; recovery_count == 1: with the
+ * XOR of all originals).
+ *
+ * *mismatch_count (required) receives the number of checked pieces that
+ * mismatch.  mismatch may be NULL; otherwise it is (recovery_count + 31) / 32
+ * words of host memory: bit j (bit j % 32 of word j / 32) is set exactly for
+ * the mismatching checked pieces, every other bit is cleared.  How to read it:
+ * one bit set -- that recovery piece is bad; every checked bit set -- an
+ * original is bad (any change of an original changes every recovery piece).
+ * Leopard_Success means "the check ran"; the verdict is in the outputs, which
+ * are written only on Leopard_Success.  With no piece to check the call
+ * returns Leopard_Success with a zero count and touches nothing on the GPU.
+ *
+ * The reports are host memory: the call returns when they are filled in, in
+ * async mode (leo_amd_set_async) too.  It runs on the calling thread's stream
+ * and device (leo_amd_set_stream / set_device), as the other extensions.
+ * All pieces are of one kind: device memory, or host memory (registered ranges
+ * are read in place, pageable memory is staged up; nothing is copied back).
+ * A host-memory call runs on one device: its columns are not fanned out
+ * (leo_amd_set_fanout does not apply).
+ *
+ * Results, in this order, all decided before any GPU work:
+ * Leopard_InvalidSize (slice form: the slice checks of leo_amd_encode_slice);
+ * Leopard_InvalidCounts (recovery_count 0 or > original_count);
+ * Leopard_InvalidInput (original_data, recovery_data or mismatch_count NULL, or
+ * a NULL original); Leopard_CallInitialize; Leopard_TooMuchData (as leo_encode).
+ *
+ * A call runs the verify form of the kernel with which leo_encode of the same
+ * shape writes the recovery pieces: it loads the stored recovery dwords where
+ * the encoder would store, compares, and ORs one bit per differing piece into
+ * a report in device memory; a clean stripe writes nothing.  The shapes without
+ * such a form (the GF(2^8) matrix path, the GF(2^16) chunk-parallel encoder of
+ * small pieces, original_count == 1, recovery_count == 1) run the composed route:
+ * the encoder into workspace scratch, a column slice at a time, then a compare
+ * kernel with the same report.  LEO_AMD_VERIFY_COMPOSE=1 (environment, read
+ * once) forces the composed route everywhere, for comparison. */
+LEO_EXPORT LeopardResult leo_amd_verify(
+    uint64_t buffer_bytes, unsigned original_count, unsigned recovery_count,
+    const void* const* original_data, const void* const* recovery_data,
+    uint32_t* mismatch, unsigned* mismatch_count);
+
+/* The same over bytes [byte_offset, byte_offset + slice_bytes) of each piece:
+ * bisects the bad column range of a large piece. */
+LEO_EXPORT LeopardResult leo_amd_verify_slice(
+    uint64_t buffer_bytes, uint64_t byte_offset, uint64_t slice_bytes,
+    unsigned original_count, unsigned recovery_count,
+    const void* const* original_data, const void* const* recovery_data,
+    uint32_t* mismatch, unsigned* mismatch_count);
+
+/* object_count objects of one shape, each with the semantics of one
+ * leo_amd_verify call: mismatch_count is an array of object_count entries and
+ * mismatch, if given, object_count rows of (recovery_count + 31) / 32 words.
+ * Every object is validated first: the first failing object's result is
+ * returned and nothing runs.  Device-resident objects on one device run as
+ * batch launches (the batch encoder's routes, then one compare launch over
+ * every object's pieces); other batches object by object. */
+LEO_EXPORT LeopardResult leo_amd_verify_batch(
+    unsigned object_count, uint64_t buffer_bytes, unsigned original_count, unsigned recovery_count,
+    const void* const* const* original_data, const void* const* const* recovery_data,
+    uint32_t* mismatch, unsigned* mismatch_count);
+
 /* Caller-registered host memory: pins [ptr, ptr + bytes) and maps it for
  * every device.  leo_encode / leo_decode calls whose host pieces all lie in
  * registered ranges run the kernels on them in place (reads and writes over

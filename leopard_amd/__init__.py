@@ -36,6 +36,7 @@ __all__ = [
     "leo_decode_work_count", "leo_decode", "leo_amd_encode_slice", "leo_amd_decode_slice", "leo_amd_encode_batch",
     "leo_amd_decode_batch", "leo_amd_update", "leo_amd_update_slice", "UPDATE_MAX_CHANGED", "update",
     "leo_amd_repair", "leo_amd_repair_slice", "leo_amd_repair_batch", "repair",
+    "leo_amd_verify", "leo_amd_verify_slice", "leo_amd_verify_batch", "verify",
     "register_host", "unregister_host", "set_fanout", "set_stream", "release_stream",
     "set_async", "set_device", "device_count", "table", "last_error", "encode", "decode", "LIB_PATH", "lib",
 ]
@@ -79,6 +80,10 @@ def _load():
         "leo_amd_repair": (i, [u64, u, u, u, pp, pp, pp, pp]),
         "leo_amd_repair_slice": (i, [u64, u64, u64, u, u, u, pp, pp, pp, pp]),
         "leo_amd_repair_batch": (i, [u, u64, u, u, u] + [ctypes.POINTER(pp)] * 4),
+        "leo_amd_verify": (i, [u64, u, u, pp, pp, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(u)]),
+        "leo_amd_verify_slice": (i, [u64, u64, u64, u, u, pp, pp, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(u)]),
+        "leo_amd_verify_batch": (i, [u, u64, u, u, ctypes.POINTER(pp), ctypes.POINTER(pp),
+                                     ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(u)]),
         "leo_amd_register_host": (i, [vp, u64]),
         "leo_amd_unregister_host": (i, [vp]),
         "leo_amd_set_stream": (None, [vp]),
@@ -254,6 +259,70 @@ def leo_amd_repair_batch(buffer_bytes, original_count, recovery_count, work_coun
                                                   arrays(recovery_out)))
 
 
+def _verify_outputs(recovery_count, objects, mismatch, count):
+    """Host outputs of a verify call.  mismatch: True = a fresh uint32 bitmap
+    (pre-filled with ones: the library writes every word), a numpy uint32 array
+    to use as given, or None / False for a NULL pointer.  count: False passes a
+    NULL mismatch_count (validation tests)."""
+    import numpy as np
+    words = (int(recovery_count) + 31) // 32
+    bitmap = None
+    if mismatch is True:
+        bitmap = np.full(max(objects, 1) * words, 0xFFFFFFFF, dtype=np.uint32)
+    elif mismatch is not None and mismatch is not False:
+        bitmap = mismatch
+        if bitmap.dtype != np.uint32 or not bitmap.flags.c_contiguous or bitmap.size < objects * words:
+            raise ValueError(f"mismatch must be a contiguous uint32 array of at least {objects * words} words")
+    counts = (ctypes.c_uint * max(objects, 1))() if count else None
+    return bitmap, counts, words
+
+
+def leo_amd_verify(buffer_bytes, original_count, recovery_count, original_data, recovery_data, mismatch=True,
+                   count=True):
+    """Check stored recovery pieces against the originals (include/leopard_amd.h); a recovery_data
+    entry None is a piece that is not checked.  Returns (LeopardResult, count, bitmap): the number of
+    mismatching checked pieces and the uint32 numpy bitmap of them (None when mismatch is None)."""
+    bitmap, counts, _ = _verify_outputs(recovery_count, 1, mismatch, count)
+    res = LeopardResult(lib.leo_amd_verify(
+        buffer_bytes, original_count, recovery_count, _opt_ptrs(original_data), _opt_ptrs(recovery_data),
+        None if bitmap is None else bitmap.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), counts))
+    return res, (int(counts[0]) if counts is not None else None), bitmap
+
+
+def leo_amd_verify_slice(buffer_bytes, byte_offset, slice_bytes, original_count, recovery_count, original_data,
+                         recovery_data, mismatch=True, count=True):
+    """leo_amd_verify over bytes [byte_offset, byte_offset + slice_bytes) of each piece."""
+    bitmap, counts, _ = _verify_outputs(recovery_count, 1, mismatch, count)
+    res = LeopardResult(lib.leo_amd_verify_slice(
+        buffer_bytes, byte_offset, slice_bytes, original_count, recovery_count, _opt_ptrs(original_data),
+        _opt_ptrs(recovery_data),
+        None if bitmap is None else bitmap.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), counts))
+    return res, (int(counts[0]) if counts is not None else None), bitmap
+
+
+def leo_amd_verify_batch(buffer_bytes, original_count, recovery_count, original_data, recovery_data, mismatch=True,
+                         count=True):
+    """One pointer sequence per object in each list (an entry None: that object's NULL array).
+    Returns (LeopardResult, [count per object], bitmap [objects, words] or None)."""
+    objects = _batch_lists(original_data=original_data, recovery_data=recovery_data)
+    bitmap, counts, words = _verify_outputs(recovery_count, objects, mismatch, count)
+
+    def arrays(seqs):
+        arrs = [_opt_ptrs(q) for q in seqs]
+        outer = (ctypes.POINTER(ctypes.c_void_p) * max(len(arrs), 1))()
+        for k, a in enumerate(arrs):
+            if a is not None:
+                outer[k] = ctypes.cast(a, ctypes.POINTER(ctypes.c_void_p))
+        outer.keep = arrs
+        return outer
+
+    res = LeopardResult(lib.leo_amd_verify_batch(
+        objects, buffer_bytes, original_count, recovery_count, arrays(original_data), arrays(recovery_data),
+        None if bitmap is None else bitmap.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), counts))
+    got = [int(counts[o]) for o in range(objects)] if counts is not None else None
+    return res, got, (None if bitmap is None else bitmap[:objects * words].reshape(objects, words))
+
+
 def register_host(ptr: int, nbytes: int) -> LeopardResult:
     """Pin + map a caller-owned host range (include/leopard_amd.h)."""
     return LeopardResult(lib.leo_amd_register_host(ctypes.c_void_p(ptr), nbytes))
@@ -396,3 +465,29 @@ def repair(original, recovery, lost_originals, lost_recovery, want_recovery=None
                          [None if j in lrs else recovery[j].data_ptr() for j in range(r)], work, rout)
     _check(res, "leo_amd_repair")
     return {i: out_o[n] for n, i in enumerate(lo)}, {j: out_r[n] for n, j in enumerate(want)}
+
+
+def verify(original, recovery, have_recovery=None):
+    """Scrub: original [K, B] / recovery [R, B] uint8 tensors of one kind (device or
+    host, rows contiguous).  have_recovery: the recovery indices to check (default:
+    all of them; rows not listed are passed as NULL and never read).  Returns the
+    sorted list of the checked recovery indices whose pieces are not what
+    leo_encode of these originals gives."""
+    if original.dim() != 2 or recovery.dim() != 2 or original.shape[1] != recovery.shape[1]:
+        raise ValueError(f"original {tuple(original.shape)} and recovery {tuple(recovery.shape)} are not "
+                         "[K, B] and [R, B] of one piece size")
+    if original.stride(1) != 1 or recovery.stride(1) != 1:
+        raise ValueError("pieces must be contiguous rows")
+    if original.device != recovery.device:
+        raise ValueError("original and recovery must be of one kind (same device)")
+    k, nbytes = original.shape
+    r = recovery.shape[0]
+    have = set(range(r)) if have_recovery is None else {int(j) for j in have_recovery}
+    if any(j < 0 or j >= r for j in have):
+        raise ValueError("a recovery index is out of range")
+    res, count, bitmap = leo_amd_verify(nbytes, k, r, [original[i].data_ptr() for i in range(k)],
+                                        [recovery[j].data_ptr() if j in have else None for j in range(r)])
+    _check(res, "leo_amd_verify")
+    bad = [j for j in range(r) if (int(bitmap[j >> 5]) >> (j & 31)) & 1]
+    assert len(bad) == count
+    return bad

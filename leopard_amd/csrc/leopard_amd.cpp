@@ -378,9 +378,12 @@ struct Workspace {
             if (sl.done) (void)hipEventDestroy(sl.done);
             sl = StageSlot{};
         }
-        release_device_memory(dev, {dbuf, ring_dev, direct, el8, bsq, rows});
+        release_device_memory(dev, {dbuf, ring_dev, direct, el8, bsq, rows, vrep});
         rows = nullptr;
         rows_size = 0;
+        if (vrep_host) (void)hipHostFree(vrep_host);
+        vrep = vrep_host = nullptr;
+        vrep_words = 0;
         if (el8_host) (void)hipHostFree(el8_host);
         el8_host = nullptr;
         for (int e = 0; e < kEl8Events; ++e) {
@@ -631,6 +634,25 @@ struct Workspace {
         rows_size = 0;
         HIP_OK(pool_alloc(reinterpret_cast<void**>(&rows), bytes, dev, stream), "allocate scratch rows");
         rows_size = bytes;
+        return Leopard_Success;
+    }
+    // Report bitmaps of leo_amd_verify: the device words its kernels OR into
+    // and their pinned host copy.  A verify call returns only when it has read
+    // the report back, so the next call finds both free.
+    uint32_t* vrep = nullptr;
+    uint32_t* vrep_host = nullptr;
+    size_t vrep_words = 0;
+    LeopardResult reserve_report(size_t words) {
+        touched = true;
+        if (words <= vrep_words) return Leopard_Success;
+        const size_t want = std::max<size_t>(words, std::max<size_t>(vrep_words * 2, 256));
+        if (vrep) HIP_OK(hipFreeAsync(vrep, stream), "free verify report");
+        if (vrep_host) HIP_OK(hipHostFree(vrep_host), "free pinned verify report");
+        vrep = vrep_host = nullptr;
+        vrep_words = 0;
+        HIP_OK(pool_alloc(reinterpret_cast<void**>(&vrep), want * 4, dev, stream), "allocate verify report");
+        HIP_OK(hipHostMalloc(reinterpret_cast<void**>(&vrep_host), want * 4, hipHostMallocDefault), "pinned verify report");
+        vrep_words = want;
         return Leopard_Success;
     }
     // Copies `bytes` from host memory src (or, with src == nullptr, lets
@@ -892,9 +914,10 @@ bool slab_of(const void* const* p, unsigned n, uint64_t& base, int32_t& stride);
 // batch tile with one object (rs_ff8_bs.hip; its persistent grid has a tile for
 // every wave from 2048 256-byte strips on).  Smaller calls keep the byte tile,
 // whose 16-wave workgroups finish one strip sooner.  *done: launched.
+// form | kFormVerify (leo_amd_verify): out = the stored pieces, read only, report = the object's bitmap.
 constexpr uint64_t kBsSingleMinBytes = 512ull << 10;
 LeopardResult dense_single_bs(Call& c, uint64_t bytes, uint64_t off, unsigned m, const void* const* in,
-                              void* const* out, int form, bool* done) {
+                              void* const* out, int form, bool* done, uint32_t* report = nullptr) {
     *done = false;
     uint64_t ib = 0, ob = 0;
     int32_t is = 0, os = 0;
@@ -913,6 +936,7 @@ LeopardResult dense_single_bs(Call& c, uint64_t bytes, uint64_t off, unsigned m,
     b.K = b.R = m;
     b.nchunks = 1;
     b.nunits = uint32_t(bytes / 4);
+    b.report = report;
     uint32_t *q = nullptr, *qclear = nullptr;
     const LeopardResult r = c.ws->bs_queue(&q, &qclear);
     if (r != Leopard_Success) return r;
@@ -939,10 +963,20 @@ void fill_enc8(Ff8EncArgs& a, const DeviceTables* t, unsigned K, unsigned R, con
     a.nunits = uint32_t(bytes / 4);
 }
 
+// The GF(2^16) narrow-strip encoder's chunk-parallel pair (encode_device below).
+bool encode16_splits(const Call& c, uint64_t bytes, unsigned K, unsigned R) {
+    const unsigned m = next_pow2(R), Tm = log2u(m);
+    return next_pow2(m + K) > 256 && encode16_small_supported(Tm) && bytes <= kNarrowColumnsMax &&
+           encode16_split_wins(Tm, (K + m - 1) / m, bytes / 8, c.t->cus);
+}
+
 // Device-resident encode of pieces [off, off + bytes) (reference:
 // leo_encode -> ff8|ff16::ReedSolomonEncode, leopard.cpp:162-197).
+// report (GF(2^16) codes off the chunk-parallel pair only, leo_amd_verify):
+// the same passes with the verify form of the kernel that writes the recovery
+// pieces; work = the stored pieces, every entry readable, none written.
 LeopardResult encode_device(Call& c, uint64_t bytes, uint64_t off, unsigned K, unsigned R, const void* const* orig,
-                            void** work) {
+                            void** work, uint32_t* report = nullptr) {
     const unsigned m = next_pow2(R);
     const unsigned n = next_pow2(m + K);
     const bool ff16 = n > 256;
@@ -983,6 +1017,7 @@ LeopardResult encode_device(Call& c, uint64_t bytes, uint64_t off, unsigned K, u
     a.R = R;
     a.Tm = Tm;
     a.nchunks = nchunks;
+    a.report = report;
     const unsigned unit_bytes = ff16 ? 8 : 4;
 
     // Multi-pass for m > 2^kLoBits; also for m = 2^kLoBits with several chunks
@@ -1002,10 +1037,11 @@ LeopardResult encode_device(Call& c, uint64_t bytes, uint64_t off, unsigned K, u
     }
     // narrow columns, several chunks, fewer 16-unit strips than CUs: the chunk
     // IFFTs in parallel workgroups through a slab of nchunks x m rows
-    const bool split = narrow && encode16_split_wins(Tm, nchunks, bytes / unit_bytes, c.t->cus);
+    const bool split = narrow && !report && encode16_split_wins(Tm, nchunks, bytes / unit_bytes, c.t->cus);
     if (split) slab_bytes = uint64_t(nchunks) * m * bytes;
     const size_t table_bytes = (mb.bytes() + 255) / 256 * 256;
-    LeopardResult r = c.ws->reserve_device(table_bytes + slab_bytes);
+    // (a narrow verify form that reads its argument block from device memory: the block behind the tables)
+    LeopardResult r = c.ws->reserve_device(table_bytes + slab_bytes + (report && narrow ? sizeof(EncArgs) : 0));
     if (r != Leopard_Success) return r;
     r = mb.flush(*c.ws, reinterpret_cast<uint64_t*>(c.ws->dbuf), c.s);
     if (r != Leopard_Success) return r;
@@ -1015,6 +1051,12 @@ LeopardResult encode_device(Call& c, uint64_t bytes, uint64_t off, unsigned K, u
         if (split) {
             a.slab_out = a.slab_in = PieceMap{nullptr, c.ws->dbuf + table_bytes, bytes, 0};
             HIP_OK(launch_encode16_split(Tm, a, c.s), "encode kernels");
+        } else if (report && verify16_small_by_value(Tm)) {
+            HIP_OK(launch_verify16_small(Tm, a, c.s), "verify kernel");
+        } else if (report) {
+            EncArgs* darg = reinterpret_cast<EncArgs*>(c.ws->dbuf + table_bytes);
+            if ((r = c.ws->upload(darg, &a, sizeof(a), c.s)) != Leopard_Success) return r;
+            HIP_OK(launch_encode16_small_batch(Tm, darg, 1, a.nunits, c.s, true), "verify kernel");
         } else {
             HIP_OK(launch_encode16_small(Tm, a, c.s), "encode kernel");
         }
@@ -1022,7 +1064,8 @@ LeopardResult encode_device(Call& c, uint64_t bytes, uint64_t off, unsigned K, u
     }
     if (!multipass) {
         a.nunits = bytes / unit_bytes;
-        HIP_OK(launch_encode_fused16(Tm, a, c.s), "encode kernel");
+        if (report) HIP_OK(launch_verify_fused16(Tm, a, c.s), "verify kernel");
+        else HIP_OK(launch_encode_fused16(Tm, a, c.s), "encode kernel");
         return Leopard_Success;
     }
     uint8_t* U = c.ws->dbuf + table_bytes;
@@ -1043,7 +1086,8 @@ LeopardResult encode_device(Call& c, uint64_t bytes, uint64_t off, unsigned K, u
         } else {
             b.slab_in = PieceMap{nullptr, U, slice, 0};
         }
-        HIP_OK(launch_encode_fin(b, c.s), "encode pass 3");
+        if (report) HIP_OK(launch_verify_fin(b, c.s), "verify pass 3");
+        else HIP_OK(launch_encode_fin(b, c.s), "encode pass 3");
     }
     return Leopard_Success;
 }
@@ -1950,7 +1994,7 @@ LeopardResult run_host_pipeline(Call& c, uint64_t bytes, const std::vector<const
         if (r != Leopard_Success) return r;
         HIP_OK(hipGetLastError(), "kernel launch");
         if ((r = cs.ws->mark_use(cs.s)) != Leopard_Success) return r;
-        if (mode == 0)
+        if (mode == 0 && nout > 0)  // (a verify call has no output rows)
             HIP_OK(hipMemcpyAsync(pin + in_bytes, dev + in_bytes, nout * slice, hipMemcpyDeviceToHost, cs.s),
                    "slice download");
         if (mode == 2) HIP_OK(hipEventRecord(ws.in_done[s], cs.s), "record input use");  // kernels read the slot
@@ -2736,7 +2780,7 @@ bool slab_on(RangeCache& rc, uint64_t base, int32_t stride, unsigned n, uint64_t
 // object is not slab-laid there.
 bool run_slab_batch8(int dev, RangeCache& rc, unsigned count, uint64_t bytes, unsigned T, unsigned K, unsigned R,
                      unsigned nin, unsigned nout, const void* const* const* ins, void* const* const* outs, bool multi,
-                     int form, LeopardResult* res) {
+                     int form, LeopardResult* res, uint32_t* report = nullptr) {
     std::vector<uint64_t> ib(count), ob(count);
     std::vector<int32_t> is(count), os(count);
     for (unsigned o = 0; o < count; ++o)
@@ -2766,8 +2810,10 @@ bool run_slab_batch8(int dev, RangeCache& rc, unsigned count, uint64_t bytes, un
                 b.out_base[j] = ob[o0 + j];
                 b.out_stride[j] = os[o0 + j];
             }
+            // verify forms (outs = the stored pieces, read only): the launch's first object's report words
+            if (report) b.report = report + size_t(o0) * ((R + 31) / 32);
             uint32_t *q = nullptr, *qclear = nullptr;
-            if (form != kFormGeneral && !multi && ff8_bs_supported(T, K, R, b.nchunks) &&
+            if ((form & ~kFormVerify) != kFormGeneral && !multi && ff8_bs_supported(T, K, R, b.nchunks) &&
                 (r = c.ws->bs_queue(&q, &qclear)) != Leopard_Success)
                 return r;
             HIP_OK(launch_ff8_encode_slab(T, b, n, multi, form, c.s, c.t->cus, q, qclear), "slab batch kernel");
@@ -2819,8 +2865,11 @@ bool narrow_decode16(unsigned K, unsigned R, uint64_t bytes) {
     return n > 256 && g_q16_ok && decode16_small_supported(log2u(n)) && bytes <= kNarrowColumnsMax;
 }
 
+// report (leo_amd_verify_batch): the verify form of the same launch; work = the
+// stored pieces, every entry readable, object o's bitmap at report + o * words.
 LeopardResult encode_batch16(int dev, unsigned count, uint64_t bytes, unsigned K, unsigned R,
-                             const void* const* const* orig, void** const* work) {
+                             const void* const* const* orig, void** const* work, uint32_t* report = nullptr,
+                             unsigned words = 0) {
     DeviceGuard guard(dev);
     Call c;
     LeopardResult r = begin_call(dev, c);
@@ -2842,13 +2891,14 @@ LeopardResult encode_batch16(int dev, unsigned count, uint64_t bytes, unsigned K
         a.Tm = Tm;
         a.nchunks = (K + m - 1) / m;
         a.nunits = bytes / 8;
+        a.report = report ? report + size_t(o) * words : nullptr;
     }
     const size_t table_bytes = (mb.bytes() + 255) / 256 * 256;
     if ((r = c.ws->reserve_device(table_bytes + count * sizeof(EncArgs))) != Leopard_Success) return r;
     if ((r = mb.flush(*c.ws, reinterpret_cast<uint64_t*>(c.ws->dbuf), c.s)) != Leopard_Success) return r;
     EncArgs* dargs = reinterpret_cast<EncArgs*>(c.ws->dbuf + table_bytes);
     if ((r = c.ws->upload(dargs, args.data(), count * sizeof(EncArgs), c.s)) != Leopard_Success) return r;
-    HIP_OK(launch_encode16_small_batch(Tm, dargs, count, bytes / 8, c.s), "batch encode kernel");
+    HIP_OK(launch_encode16_small_batch(Tm, dargs, count, bytes / 8, c.s, report != nullptr), "batch encode kernel");
     return finish(c, false);
 }
 
@@ -3489,6 +3539,443 @@ LeopardResult repair_batch(unsigned count, uint64_t bytes, unsigned K, unsigned 
     return Leopard_Success;
 }
 
+// --------------------------------------------------------------- verify ----
+// leo_amd_verify: do the stored recovery pieces still belong to the originals?
+// The verdict is a bitmap of the checked pieces that differ from what the
+// encoder computes: kernels OR bits into the workspace's report words (zeroed
+// on the stream in front of them), the call reads them back through pinned
+// memory and always returns with the host reports filled in.
+//
+// Composed route (every shape): the existing encoder into workspace scratch,
+// one column slice at a time, then the compare kernel (rs_verify.hip).
+
+// Experiment builds: leo_amd_exp_verify_route(0 | 1) forces the fused / the
+// composed route for the calls that follow, -1 returns to the environment's
+// choice (tools/bench_verify.py alternates the routes in one process).
+#if LAMD_EXPERIMENT_ENV
+std::atomic<int> g_verify_route{-1};
+#endif
+// LEO_AMD_VERIFY_COMPOSE=1 forces the composed route; read once.
+bool verify_compose_forced() {
+#if LAMD_EXPERIMENT_ENV
+    if (g_verify_route.load() >= 0) return g_verify_route.load() == 1;
+#endif
+    static const bool v = [] {
+        const char* e = std::getenv("LEO_AMD_VERIFY_COMPOSE");
+        return e && e[0] == '1';
+    }();
+    return v;
+}
+unsigned verify_words(unsigned R) { return (R + 31) / 32; }
+
+// The library's own nested calls (the batch encoder under a batch verify)
+// enqueue and return: the verify call synchronises once, at its end.
+struct AsyncScope {
+    bool prev;
+    AsyncScope() : prev(tls.async) { tls.async = true; }
+    ~AsyncScope() { tls.async = prev; }
+};
+
+// Large scratch rows do not stay with the thread (as repair_compose).
+void trim_rows(Call& c) {
+    Workspace& ws = *c.ws;
+    if (ws.rows_size > kDirectKeepBytes) {
+        (void)hipFreeAsync(ws.rows, c.s);
+        ws.rows = nullptr;
+        ws.rows_size = 0;
+    }
+}
+
+// Device-visible pieces, columns [off, off + bytes): the encoder's output for
+// a column slice in scratch rows of the workspace (R x slice bytes, bounded by
+// mall_slice), compared with the stored pieces.  K == 1: nothing to compute,
+// every checked piece is compared with the original.  report: the words of
+// this object (they may belong to another workspace: the staged host path).
+LeopardResult verify_compose(Call& c, uint64_t bytes, uint64_t off, unsigned K, unsigned R, const void* const* orig,
+                             const void* const* rec, uint32_t* report) {
+    Workspace& ws = *c.ws;
+    // Slices of mall_slice, and no more scratch than stays with the thread
+    // (kDirectKeepBytes): rows above that are freed and allocated again by
+    // every call, which at 2 GiB of rows (32768+32768 x 64 KiB) takes 73-89 ms
+    // a call where the encoder alone takes 3.7.
+    const size_t table_bytes = (size_t(R) * 8 + 255) / 256 * 256;
+    const uint64_t keep = std::max<uint64_t>((kDirectKeepBytes - table_bytes) / R / 512 * 512, 512);
+    const uint64_t slice = K == 1 ? bytes : std::min(mall_slice(bytes, R), keep);
+    LeopardResult r = ws.reserve_rows(table_bytes + (K == 1 ? 0 : size_t(R) * slice));
+    if (r != Leopard_Success) return r;
+    uint64_t* table = reinterpret_cast<uint64_t*>(ws.rows);
+    uint8_t* rows = ws.rows + table_bytes;
+    r = ws.upload(table, size_t(R) * 8, c.s, [&](uint8_t* h) {
+        uint64_t* t = reinterpret_cast<uint64_t*>(h);
+        for (unsigned j = 0; j < R; ++j) t[j] = rec[j] ? uint64_t(reinterpret_cast<uintptr_t>(rec[j])) + off : 0;
+    });
+    if (r != Leopard_Success) return r;
+    std::vector<void*> w(R);
+    for (uint64_t pos = 0; pos < bytes; pos += slice) {
+        const uint64_t len = std::min(slice, bytes - pos);
+        VerifyCmpArgs a;
+        std::memset(&a, 0, sizeof(a));
+        a.stored = table;
+        a.col0 = pos;
+        a.n16 = len / 16;
+        a.report = report;
+        a.pairs = a.R = R;
+        a.words = verify_words(R);
+        if (K == 1) {
+            a.calc_base = static_cast<const uint8_t*>(orig[0]) + off + pos;
+        } else {
+            a.calc_base = rows;
+            a.calc_stride = slice;
+            for (unsigned j = 0; j < R; ++j) w[j] = rows + uint64_t(j) * slice - (off + pos);  // the encoder adds off + pos
+            r = R == 1 ? xor_device(c, len, off + pos, orig, K, w[0]) : encode_device(c, len, off + pos, K, R, orig, w.data());
+            if (r != Leopard_Success) return r;
+        }
+        HIP_OK(launch_verify_cmp(a, c.t->cus, c.s), "verify compare kernel");
+    }
+    trim_rows(c);
+    return Leopard_Success;
+}
+
+// Fused routes: the verify form of the encoder tile the same call of
+// leo_encode would run (encode_device's route conditions), which loads the
+// stored pieces where the encoder stores and writes nothing but report bits.
+// Routes without a verify form stay composed: the matrix path, the GF(2^16)
+// chunk-parallel pair, K == 1 and R == 1.
+//
+// Where a call that has a fused route takes the composition instead: nowhere
+// but under LEO_AMD_VERIFY_COMPOSE=1 (so =0 has nothing to override).
+// Measured (profiles/verify/bench_verify.jsonl), fused /
+// composed us per call, alternating in one process: 128+128 x 64 KiB 38.0 /
+// 46.0, 128+128 x 1 MiB (bit-sliced single) 80.2 / 126.7, 64 slab-laid objects
+// of 128+128 x 64 KiB (bit-sliced batch) 487 / 748, 1000+200 x 64 KiB (k_enc16n)
+// 77.0 / 90.2, 32768+32768 x 64 KiB (three passes, k_enc_fin) 3769 / 4780; each
+// ahead by several times the rounds' spread.
+bool verify_composes() { return verify_compose_forced(); }
+
+// The stored pieces of a GF(2^16) verify form: its loads are branch-free, so a
+// piece that is not checked reads the first checked one (verify_report drops
+// the bits of unchecked pieces).
+std::vector<void*> readable_pieces(const void* const* rec, unsigned R) {
+    std::vector<void*> p(R);
+    const void* any = nullptr;
+    for (unsigned j = 0; j < R && !any; ++j) any = rec[j];
+    for (unsigned j = 0; j < R; ++j) p[j] = const_cast<void*>(rec[j] ? rec[j] : any);
+    return p;
+}
+
+// GF(2^8) verify argument block of one object (fill_enc8 with the stored
+// pieces in the output positions; 0: not checked).
+void fill_ver8(Ff8EncArgs& a, const DeviceTables* t, unsigned K, unsigned R, const void* const* orig,
+               const void* const* rec, uint64_t off, uint64_t bytes, uint32_t* report) {
+    const unsigned m = next_pow2(R);
+    std::memset(&a, 0, sizeof(a));
+    for (unsigned i = 0; i < K; ++i) a.ptr[i] = uint64_t(reinterpret_cast<uintptr_t>(orig[i])) + off;
+    for (unsigned j = 0; j < R; ++j) a.ptr[K + j] = rec[j] ? uint64_t(reinterpret_cast<uintptr_t>(rec[j])) + off : 0;
+    a.sktab = t->sktab8;
+    a.fused = t->fused8 + size_t(log2u(m) - 1) * 256 * kTab8Dwords;
+    a.K = K;
+    a.R = R;
+    a.nchunks = (K + m - 1) / m;
+    a.nunits = uint32_t(bytes / 4);
+    a.report = report;
+}
+
+// *done: the check was launched on a fused route.
+LeopardResult verify_fused(Call& c, uint64_t bytes, uint64_t off, unsigned K, unsigned R, const void* const* orig,
+                           const void* const* rec, uint32_t* report, bool* done) {
+    *done = false;
+    if (K == 1 || R == 1 || verify_composes()) return Leopard_Success;
+    const unsigned m = next_pow2(R);
+    const unsigned n = next_pow2(m + K);
+    const unsigned Tm = log2u(m);
+    const unsigned nchunks = (K + m - 1) / m;
+    if (n <= 256) {
+        // dense 128 + 128 on large slab-laid pieces, every piece checked: the bit-sliced tile
+        bool all = true;
+        for (unsigned j = 0; j < R; ++j) all = all && rec[j];
+        if (K == R && nchunks == 1 && all) {
+            const LeopardResult r = dense_single_bs(c, bytes, off, m, orig, const_cast<void* const*>(rec),
+                                                    kFormDenseEnc | kFormVerify, done, report);
+            if (r != Leopard_Success || *done) return r;
+        }
+        // the encoder would take the matrix path: composed
+        if (use_matrix(R, K, bytes, nchunks >= 3, false) && (nchunks >= 2 || bytes <= kMatSmallBytes))
+            return Leopard_Success;
+        Ff8EncArgs a;
+        for (uint64_t pos = 0; pos < bytes; pos += kFf8MaxLaunchBytes) {
+            fill_ver8(a, c.t, K, R, orig, rec, off + pos, std::min(kFf8MaxLaunchBytes, bytes - pos), report);
+            HIP_OK(launch_ff8_verify(Tm, a, c.s), "verify kernel");
+        }
+        *done = true;
+        return Leopard_Success;
+    }
+    // GF(2^16): encode_device's passes with the verify form of the kernel that writes the recovery pieces
+    // (k_enc16n, k_enc_fused, k_enc_fin); the chunk-parallel k_enc16n_part / k_enc16n_comb pair stays composed
+    if (encode16_splits(c, bytes, K, R)) return Leopard_Success;
+    std::vector<void*> stored = readable_pieces(rec, R);
+    const LeopardResult r = encode_device(c, bytes, off, K, R, orig, stored.data(), report);
+    *done = r == Leopard_Success;
+    return r;
+}
+
+LeopardResult verify_device(Call& c, uint64_t bytes, uint64_t off, unsigned K, unsigned R, const void* const* orig,
+                            const void* const* rec, uint32_t* report) {
+    bool done = false;
+    const LeopardResult r = verify_fused(c, bytes, off, K, R, orig, rec, report, &done);
+    if (r != Leopard_Success || done) return r;
+    return verify_compose(c, bytes, off, K, R, orig, rec, report);
+}
+
+// Validation of one object, in the header's order.
+LeopardResult check_verify(uint64_t bytes, unsigned K, unsigned R, const void* const* orig, const void* const* rec,
+                           const unsigned* count_out) {
+    if (bytes == 0 || bytes % 64 != 0) return Leopard_InvalidSize;
+    if (R == 0 || R > K) return Leopard_InvalidCounts;
+    if (!orig || !rec || !count_out) {
+        tls.last_error = std::string(!orig ? "original_data" : !rec ? "recovery_data" : "mismatch_count") + " is NULL";
+        return Leopard_InvalidInput;
+    }
+    for (unsigned i = 0; i < K; ++i)
+        if (!orig[i]) {
+            char buf[96];
+            std::snprintf(buf, sizeof(buf), "original_data[%u] is NULL: verify needs every original", i);
+            tls.last_error = buf;
+            return Leopard_InvalidInput;
+        }
+    if (!g_initialized) return Leopard_CallInitialize;
+    if (K > 1 && R > 1 && next_pow2(next_pow2(R) + K) > 65536) return Leopard_TooMuchData;
+    return Leopard_Success;
+}
+
+// Bits of the checked pieces only (the kernels never set another one), counted.
+unsigned verify_report(unsigned R, const void* const* rec, const uint32_t* got, uint32_t* mismatch) {
+    unsigned n = 0;
+    for (unsigned w = 0; w < verify_words(R); ++w) {
+        uint32_t m = 0;
+        for (unsigned j = w * 32; j < std::min(R, w * 32 + 32); ++j)
+            if (rec[j]) m |= 1u << (j & 31u);
+        m &= got[w];
+        n += unsigned(__builtin_popcount(m));
+        if (mismatch) mismatch[w] = m;
+    }
+    return n;
+}
+
+// One validated object: columns [off, off + bytes) of every piece.
+LeopardResult verify_any(uint64_t bytes, uint64_t off, unsigned K, unsigned R, const void* const* orig,
+                         const void* const* rec, uint32_t* mismatch, unsigned* count_out) {
+    const unsigned words = verify_words(R);
+    bool any = false;
+    for (unsigned j = 0; j < R; ++j) any = any || rec[j];
+    if (!any) {  // nothing to check: no GPU work
+        *count_out = 0;
+        if (mismatch) std::memset(mismatch, 0, words * 4);
+        return Leopard_Success;
+    }
+    MemKind kind;
+    const int dev = pick_device(orig[0], &kind);
+    DeviceGuard guard(dev);
+    Call c;
+    LeopardResult r = begin_call(dev, c);
+    if (r != Leopard_Success) return r;
+    Workspace& ws = *c.ws;
+    if ((r = ws.reserve_report(words)) != Leopard_Success) return r;
+    HIP_OK(hipMemsetAsync(ws.vrep, 0, words * 4, c.s), "clear verify report");
+    if (kind == MemKind::Device) {
+        if ((r = verify_device(c, bytes, off, K, R, orig, rec, ws.vrep)) != Leopard_Success) return r;
+    } else {
+        // host memory, on one device (no fan-out).  The staged slices run on
+        // streams of their own: the cleared report is in place before them.
+        HIP_OK(hipStreamSynchronize(c.s), "stream synchronize");
+        std::vector<void*> dorig, drec;
+        if (map_registered(orig, K, off, bytes, dorig) && map_registered(rec, R, off, bytes, drec)) {
+            // caller-registered host memory: the kernels read it in place
+            r = verify_device(c, bytes, off, K, R, const_cast<const void* const*>(dorig.data()),
+                              const_cast<const void* const*>(drec.data()), ws.vrep);
+            if (r != Leopard_Success) return r;
+        } else {
+            // pageable memory staged as dense rows: the originals, then the checked pieces; nothing comes back
+            std::vector<const uint8_t*> hin;
+            std::vector<int> in_rec(R, -1);
+            for (unsigned i = 0; i < K; ++i) hin.push_back(static_cast<const uint8_t*>(orig[i]) + off);
+            for (unsigned j = 0; j < R; ++j)
+                if (rec[j]) {
+                    in_rec[j] = int(hin.size());
+                    hin.push_back(static_cast<const uint8_t*>(rec[j]) + off);
+                }
+            uint32_t* report = ws.vrep;
+            const SliceFn slice_fn = [&](Call& cs, uint64_t len, uint8_t* din, uint8_t*, uint64_t stride) {
+                std::vector<const void*> di(K), dr(R, nullptr);
+                for (unsigned i = 0; i < K; ++i) di[i] = din + i * stride;
+                for (unsigned j = 0; j < R; ++j)
+                    if (in_rec[j] >= 0) dr[j] = din + in_rec[j] * stride;
+                return verify_device(cs, len, 0, K, R, di.data(), dr.data(), report);
+            };
+            if ((r = run_host_pipeline(c, bytes, hin, std::vector<uint8_t*>(), slice_fn)) != Leopard_Success) return r;
+        }
+    }
+    HIP_OK(hipMemcpyAsync(ws.vrep_host, ws.vrep, words * 4, hipMemcpyDeviceToHost, c.s), "read back verify report");
+    if ((r = finish(c, true)) != Leopard_Success) return r;
+    *count_out = verify_report(R, rec, ws.vrep_host, mismatch);
+    return Leopard_Success;
+}
+
+// Scratch rows of one composed batch launch sequence (objects x R x bytes).
+constexpr uint64_t kVerifyBatchRowsBytes = 192ull << 20;  // with the table, under kDirectKeepBytes: the rows stay with the thread
+
+LeopardResult verify_batch(unsigned count, uint64_t bytes, unsigned K, unsigned R, const void* const* const* orig,
+                           const void* const* const* rec, uint32_t* mismatch, unsigned* counts) {
+    if (bytes == 0 || bytes % 64 != 0) return Leopard_InvalidSize;
+    if (R == 0 || R > K) return Leopard_InvalidCounts;
+    if (!orig || !rec || !counts) {
+        tls.last_error = std::string(!orig ? "original_data" : !rec ? "recovery_data" : "mismatch_count") + " is NULL";
+        return Leopard_InvalidInput;
+    }
+    for (unsigned o = 0; o < count; ++o) {
+        const LeopardResult r = check_verify(bytes, K, R, orig[o], rec[o], counts);
+        if (r != Leopard_Success) return r;
+    }
+    const unsigned words = verify_words(R);
+    std::vector<unsigned> todo;  // the objects with a piece to check
+    for (unsigned o = 0; o < count; ++o) {
+        bool any = false;
+        for (unsigned j = 0; j < R; ++j) any = any || rec[o][j];
+        if (any) {
+            todo.push_back(o);
+        } else {
+            counts[o] = 0;
+            if (mismatch) std::memset(mismatch + size_t(o) * words, 0, words * 4);
+        }
+    }
+    if (todo.empty()) return Leopard_Success;
+    if (K > 1 && R > 1) {
+        // device-resident objects on one device: the batch encoder into scratch
+        // rows (its own routes: slab launches, bit-sliced tile, pointer tables,
+        // the GF(2^16) narrow batch), then one compare launch over every pair
+        MemKind kind = MemKind::Host;
+        const int dev = pick_device(orig[todo[0]][0], &kind);
+        RangeCache rc;
+        bool on_dev = kind == MemKind::Device;
+        for (size_t t = 0; t < todo.size() && on_dev; ++t)
+            on_dev = rc.all_on(orig[todo[t]], K, bytes, dev) && rc.all_on(rec[todo[t]], R, bytes, dev);
+        if (on_dev) {
+            DeviceGuard guard(dev);
+            Call c;
+            LeopardResult r = begin_call(dev, c);
+            if (r != Leopard_Success) return r;
+            Workspace& ws = *c.ws;
+            const size_t nt = todo.size();
+            if ((r = ws.reserve_report(nt * words)) != Leopard_Success) return r;
+            HIP_OK(hipMemsetAsync(ws.vrep, 0, nt * words * 4, c.s), "clear verify report");
+            const unsigned m = next_pow2(R), n = next_pow2(m + K), Tm = log2u(m);
+            std::vector<const void* const*> fo(nt), fr(nt);
+            for (size_t t = 0; t < nt; ++t) {
+                fo[t] = orig[todo[t]];
+                fr[t] = rec[todo[t]];
+            }
+            bool fused = false;
+            if (n <= 256 && bytes <= kFf8MaxLaunchBytes && !verify_composes()) {
+                // GF(2^8): the verify form of the batch encoder's tile, as encode_batch picks it: slab-laid
+                // objects (every piece checked) by value, 64 a launch, bit-sliced where ff8_bs_supported;
+                // else one launch over the objects' pointer tables
+                const bool multi = (K + m - 1) / m > 1;
+                const int form = (K == m && R == m ? kFormDenseEnc : kFormGeneral) | kFormVerify;
+                bool all = true;
+                for (size_t t = 0; t < nt && all; ++t)
+                    for (unsigned j = 0; j < R && all; ++j) all = fr[t][j] != nullptr;
+                std::vector<void* const*> outs(nt);
+                for (size_t t = 0; t < nt; ++t) outs[t] = const_cast<void* const*>(fr[t]);
+                AsyncScope enqueue_only;
+                if (!all || !run_slab_batch8(dev, rc, unsigned(nt), bytes, Tm, K, R, K, R, fo.data(), outs.data(), multi,
+                                             form, &r, ws.vrep))
+                    r = run_batch8<Ff8EncArgs>(
+                        dev, unsigned(nt),
+                        [&](Ff8EncArgs& a, const DeviceTables* t, unsigned o) {
+                            fill_ver8(a, t, K, R, fo[o], fr[o], 0, bytes, ws.vrep + size_t(o) * words);
+                            return 0;
+                        },
+                        [&](const Ff8EncArgs* d, int, hipStream_t s) {
+                            return launch_ff8_encode_batch(Tm, d, unsigned(nt), uint32_t(bytes / 4), multi, form, s);
+                        });
+                if (r != Leopard_Success) return r;
+                fused = true;
+            } else if (narrow_encode16(K, R, bytes) && !verify_composes()) {
+                // GF(2^16) narrow batch: the verify form of k_enc16n_batch, one grid over every object
+                std::vector<std::vector<void*>> st(nt);
+                std::vector<void**> fw(nt);
+                for (size_t t = 0; t < nt; ++t) {
+                    st[t] = readable_pieces(fr[t], R);
+                    fw[t] = st[t].data();
+                }
+                AsyncScope enqueue_only;
+                if ((r = encode_batch16(dev, unsigned(nt), bytes, K, R, fo.data(), fw.data(), ws.vrep, words)) != Leopard_Success)
+                    return r;
+                fused = true;
+            }
+            // composed: the batch encoder into scratch rows (its own routes: slab launches, bit-sliced
+            // tile, pointer tables, the GF(2^16) narrow batch), then one compare launch over every pair
+            const uint64_t obj_bytes = uint64_t(R) * bytes;
+            const bool sliced = !fused && obj_bytes > kVerifyBatchRowsBytes;  // below: object by object, in column slices
+            const size_t per =
+                fused || sliced ? 0 : size_t(std::max<uint64_t>(1, std::min<uint64_t>(nt, kVerifyBatchRowsBytes / obj_bytes)));
+            const size_t table_bytes = (per * R * 8 + 255) / 256 * 256;
+            if (per && (r = ws.reserve_rows(table_bytes + per * obj_bytes)) != Leopard_Success) return r;
+            uint64_t* table = reinterpret_cast<uint64_t*>(ws.rows);
+            uint8_t* rows = ws.rows + table_bytes;
+            std::vector<std::vector<void*>> w(per, std::vector<void*>(2 * m, nullptr));
+            std::vector<void**> fw(per);
+            for (size_t b = 0; b < per; ++b) {
+                for (unsigned j = 0; j < R; ++j) w[b][j] = rows + (b * R + j) * bytes;
+                fw[b] = w[b].data();
+            }
+            for (size_t t0 = 0; per && t0 < nt; t0 += per) {
+                const size_t nb = std::min(per, nt - t0);
+                r = ws.upload(table, nb * R * 8, c.s, [&](uint8_t* h) {
+                    uint64_t* t = reinterpret_cast<uint64_t*>(h);
+                    for (size_t b = 0; b < nb; ++b)
+                        for (unsigned j = 0; j < R; ++j) t[b * R + j] = uint64_t(reinterpret_cast<uintptr_t>(fr[t0 + b][j]));
+                });
+                if (r != Leopard_Success) return r;
+                {
+                    AsyncScope enqueue_only;
+                    r = encode_batch(unsigned(nb), bytes, K, R, 2 * m, fo.data() + t0, fw.data());
+                }
+                if (r != Leopard_Success) return r;
+                VerifyCmpArgs a;
+                std::memset(&a, 0, sizeof(a));
+                a.stored = table;
+                a.calc_base = rows;
+                a.calc_stride = bytes;
+                a.n16 = bytes / 16;
+                a.report = ws.vrep + t0 * words;
+                a.pairs = unsigned(nb * R);
+                a.R = R;
+                a.words = words;
+                ws.touched = true;
+                HIP_OK(launch_verify_cmp(a, c.t->cus, c.s), "verify compare kernel");
+            }
+            if (per) trim_rows(c);
+            for (size_t t = 0; sliced && t < nt; ++t)
+                if ((r = verify_device(c, bytes, 0, K, R, fo[t], fr[t], ws.vrep + t * words)) != Leopard_Success) return r;
+            ws.touched = true;
+            HIP_OK(hipMemcpyAsync(ws.vrep_host, ws.vrep, nt * words * 4, hipMemcpyDeviceToHost, c.s),
+                   "read back verify report");
+            if ((r = finish(c, true)) != Leopard_Success) return r;
+            for (size_t t = 0; t < nt; ++t) {
+                const unsigned o = todo[t];
+                counts[o] = verify_report(R, rec[o], ws.vrep_host + t * words, mismatch ? mismatch + size_t(o) * words : nullptr);
+            }
+            return Leopard_Success;
+        }
+    }
+    for (unsigned o : todo) {
+        const LeopardResult r =
+            verify_any(bytes, 0, K, R, orig[o], rec[o], mismatch ? mismatch + size_t(o) * words : nullptr, counts + o);
+        if (r != Leopard_Success) return r;
+    }
+    return Leopard_Success;
+}
+
 }  // namespace
 }  // namespace lamd
 
@@ -3677,6 +4164,41 @@ LEO_EXPORT LeopardResult leo_amd_repair_batch(unsigned object_count, uint64_t bu
     return repair_batch(object_count, buffer_bytes, original_count, recovery_count, work_count, original_data,
                         recovery_data, work_data, recovery_out);
 }
+
+LEO_EXPORT LeopardResult leo_amd_verify(uint64_t buffer_bytes, unsigned original_count, unsigned recovery_count,
+                                        const void* const* original_data, const void* const* recovery_data,
+                                        uint32_t* mismatch, unsigned* mismatch_count) {
+    const LeopardResult r =
+        check_verify(buffer_bytes, original_count, recovery_count, original_data, recovery_data, mismatch_count);
+    if (r != Leopard_Success) return r;
+    return verify_any(buffer_bytes, 0, original_count, recovery_count, original_data, recovery_data, mismatch,
+                      mismatch_count);
+}
+
+LEO_EXPORT LeopardResult leo_amd_verify_slice(uint64_t buffer_bytes, uint64_t byte_offset, uint64_t slice_bytes,
+                                              unsigned original_count, unsigned recovery_count,
+                                              const void* const* original_data, const void* const* recovery_data,
+                                              uint32_t* mismatch, unsigned* mismatch_count) {
+    if (slice_bytes == 0 || slice_bytes % 64 || byte_offset % 64 || byte_offset + slice_bytes > buffer_bytes)
+        return Leopard_InvalidSize;
+    const LeopardResult r =
+        check_verify(buffer_bytes, original_count, recovery_count, original_data, recovery_data, mismatch_count);
+    if (r != Leopard_Success) return r;
+    return verify_any(slice_bytes, byte_offset, original_count, recovery_count, original_data, recovery_data, mismatch,
+                      mismatch_count);
+}
+
+LEO_EXPORT LeopardResult leo_amd_verify_batch(unsigned object_count, uint64_t buffer_bytes, unsigned original_count,
+                                              unsigned recovery_count, const void* const* const* original_data,
+                                              const void* const* const* recovery_data, uint32_t* mismatch,
+                                              unsigned* mismatch_count) {
+    return verify_batch(object_count, buffer_bytes, original_count, recovery_count, original_data, recovery_data,
+                        mismatch, mismatch_count);
+}
+
+#if LAMD_EXPERIMENT_ENV
+LEO_EXPORT void leo_amd_exp_verify_route(int route) { g_verify_route.store(route < 0 ? -1 : route != 0); }
+#endif
 
 LEO_EXPORT LeopardResult leo_amd_register_host(void* ptr, uint64_t bytes) {
     if (!ptr || bytes == 0) return Leopard_InvalidInput;

@@ -28,6 +28,7 @@ struct EncArgs {
     const uint32_t* fused;  // FF16: fused top-layer table index per chunk of this m (gf_tables.h)
     unsigned K, R, Tm, nchunks;
     uint64_t nunits;  // column units in this launch
+    uint32_t* report;  // verify forms: the object's mismatch bitmap, (R + 31) / 32 words; out = the stored pieces
 };
 
 struct DecArgs {
@@ -66,6 +67,7 @@ struct Ff8EncArgs {
     const uint32_t* fused;   // fused top-layer tables of this m, entry c for chunk c (8 dwords)
     unsigned K, R, nchunks;
     uint32_t nunits;         // dword columns per piece in this launch
+    uint32_t* report;        // verify forms: the object's mismatch bitmap, (R + 31) / 32 words (else unused)
     __host__ __device__ uint64_t piece(unsigned i) const { return ptr[i]; }
     static constexpr bool kSlab = false;
     __host__ __device__ uint64_t in_piece(unsigned i) const { return ptr[i]; }       // i < K
@@ -85,6 +87,7 @@ struct Ff8SlabBatch {
     const uint32_t* fused;
     unsigned K, R, nchunks;
     uint32_t nunits;
+    uint32_t* report;  // verify forms: object o's bitmap at report + o * ((R + 31) / 32) (else unused)
 };
 // One object of a slab batch with the interface of Ff8EncArgs (rs_ff8.hip: ff8_enc).
 struct Ff8SlabView {
@@ -94,9 +97,11 @@ struct Ff8SlabView {
     const uint32_t* fused;
     unsigned K, R, nchunks;
     uint32_t nunits;
+    uint32_t* report;
     __host__ __device__ Ff8SlabView(const Ff8SlabBatch& b, unsigned o)
         : in_base(b.in_base[o]), out_base(b.out_base[o]), in_stride(b.in_stride[o]), out_stride(b.out_stride[o]),
-          sktab(b.sktab), fused(b.fused), K(b.K), R(b.R), nchunks(b.nchunks), nunits(b.nunits) {}
+          sktab(b.sktab), fused(b.fused), K(b.K), R(b.R), nchunks(b.nchunks), nunits(b.nunits),
+          report(b.report + size_t(o) * ((b.R + 31) / 32)) {}
     static constexpr bool kSlab = true;  // piece i + 1 = piece i + stride
     __host__ __device__ uint64_t piece(unsigned i) const { return i < K ? in_piece(i) : out_piece(i - K); }
     __host__ __device__ uint64_t in_piece(unsigned i) const { return in_base + uint64_t(int64_t(i) * in_stride); }
@@ -151,6 +156,9 @@ constexpr size_t kEl8Dwords = kFf8Ptrs / 4;
 // dense encode (one chunk, K = R = m), dense inverse (full-loss decode of a
 // K = R = m code, launch_ff8_decode_full).
 constexpr int kFormGeneral = 0, kFormDenseEnc = 1, kFormDenseDec = 2;
+// ... | kFormVerify: the verify form of an encode tile (leo_amd_verify): stored
+// recovery pieces are compared with the computed ones instead of written.
+constexpr int kFormVerify = 4;
 
 struct XorArgs {
     PieceMap src;
@@ -167,6 +175,11 @@ hipError_t launch_encode_fused16(unsigned T, const EncArgs& a, hipStream_t s);
 hipError_t launch_encode_lo(const EncArgs& a, hipStream_t s);
 hipError_t launch_encode_hi(const EncArgs& a, hipStream_t s);
 hipError_t launch_encode_fin(const EncArgs& a, hipStream_t s);
+// verify forms of the kernels that write the recovery pieces (a.report; a.out = the stored pieces, every entry readable)
+hipError_t launch_verify_fused16(unsigned T, const EncArgs& a, hipStream_t s);
+hipError_t launch_verify_fin(const EncArgs& a, hipStream_t s);
+hipError_t launch_verify16_small(unsigned Tm, const EncArgs& a, hipStream_t s);  // where verify16_small_by_value(Tm),
+bool verify16_small_by_value(unsigned Tm);  // else launch_encode16_small_batch(..., verify) on one uploaded block
 hipError_t launch_decode_lo(const DecArgs& a, hipStream_t s);
 hipError_t launch_decode_hi(const DecArgs& a, hipStream_t s);
 // repair: lost recovery positions marked in a.needed_pyr are revealed into a.rec_out
@@ -194,7 +207,7 @@ hipError_t launch_decode16_small_fin(const DecArgs& a, hipStream_t s);
 // batches of `count` objects of one shape, argument blocks in device memory
 // (object = blockIdx.y; pass 1 of the decoder: blockIdx.z)
 hipError_t launch_encode16_small_batch(unsigned Tm, const EncArgs* objs, unsigned count, uint64_t nunits,
-                                       hipStream_t s);
+                                       hipStream_t s, bool verify = false);
 hipError_t launch_decode16_small_batch(const DecArgs* objs, unsigned count, uint64_t nunits, unsigned nlo,
                                        unsigned nout, hipStream_t s);
 // one pass (scale + low IFFT per received tile folded into per-lane Z
@@ -203,6 +216,8 @@ bool decode16_one_supported(unsigned nout);
 hipError_t launch_decode16_one(const DecArgs& a, hipStream_t s);
 hipError_t launch_decode16_one_batch(const DecArgs* objs, unsigned count, uint64_t nunits, hipStream_t s);
 hipError_t launch_ff8_encode(unsigned T, const Ff8EncArgs& a, hipStream_t s);
+// the verify form of the tile launch_ff8_encode picks (a.report; ptr[K + j] == 0: piece j is not checked)
+hipError_t launch_ff8_verify(unsigned T, const Ff8EncArgs& a, hipStream_t s);
 hipError_t launch_ff8_decode(unsigned T, const Ff8DecArgs& a, hipStream_t s);
 hipError_t launch_error_locator8(const El8Args& a, unsigned count, hipStream_t s);
 // Batched GF(2^8) launches: `count` argument blocks in device memory (same T,
@@ -275,6 +290,21 @@ struct UpdTabArgs {
     uint32_t logs;  // GF(2^16): write the table index (a dword per output) instead of the table
 };
 hipError_t launch_update_tabs(bool ff16, const UpdTabArgs& a, hipStream_t s);
+
+// Compare kernel of leo_amd_verify's composed route (rs_verify.hip): pair p <
+// pairs compares the computed piece calc_base + p * calc_stride with the stored
+// piece stored[p] + col0 (0: not checked) over n16 16-byte columns, and ORs bit
+// p % R of row p / R (rows of `words` dwords) into report where they differ.
+struct VerifyCmpArgs {
+    const uint64_t* stored;  // device table of `pairs` piece addresses
+    const uint8_t* calc_base;
+    uint64_t calc_stride;
+    uint64_t col0;           // byte offset of the launch's columns inside the stored pieces
+    uint64_t n16;
+    uint32_t* report;
+    unsigned pairs, R, words;
+};
+hipError_t launch_verify_cmp(const VerifyCmpArgs& a, unsigned cus, hipStream_t s);
 
 // Units per lane chosen for each kernel family (the host sizes grids with it).
 constexpr int kUnitsPerLane = 1;

@@ -95,6 +95,21 @@ LDEV void st_unit(uint8_t* piece, uint64_t off, const uint32_t* x) {
     gst<uint32_t>(piece + off + 32, x[1]);
 }
 
+// Verify forms (leo_amd_verify): a wave's lanes hold 64 / LW pieces, one per
+// group of LW lanes (tp is the lane's own piece), so the ballot is cut into the
+// groups: the first lane of a group that saw a difference ORs its piece's bit
+// into the object's report.  No write on a clean piece.
+template <int LW>
+LDEV void flag_piece(uint32_t* report, unsigned tp, bool diff) {
+    uint64_t bad = __builtin_amdgcn_ballot_w64(diff);
+    unsigned l = threadIdx.x & 63u;
+    if constexpr (LW < 64) {
+        bad = (bad >> (l & ~unsigned(LW - 1))) & ((1ull << LW) - 1);
+        l &= unsigned(LW - 1);
+    }
+    if (bad != 0 && l == unsigned(__builtin_ctzll(bad))) atomicOr(report + (tp >> 5), 1u << (tp & 31u));
+}
+
 constexpr int lg2(unsigned v) { return v <= 1 ? 0 : 1 + lg2(v >> 1); }
 constexpr int lg_bits(int LW) { return LW == 64 ? 0 : LW == 32 ? 1 : LW == 16 ? 2 : 3; }
 template <int T, int R, int LW>
@@ -155,7 +170,11 @@ LDEV void dma_skew_set(uint32_t* set, const uint32_t* sktab, unsigned hi_fixed, 
 #endif
 constexpr bool kEncDma = LAMD_ENC16N_DMA;
 
-template <int T, int R, int LW>
+// kVerify: the verify form (leo_amd_verify).  a.out holds the stored recovery
+// pieces; they are loaded from the addresses the encoder stores to, XORed with
+// the computed values and flagged per piece in a.report (per lane group: the
+// lanes of a wave hold 2^G pieces).  Nothing is written on a clean stripe.
+template <int T, int R, int LW, bool kVerify = false>
 LDEV void enc16n_body(const EncArgs& a) {
     if constexpr ((LAMD_ABLATE & 16) != 0) return;
     constexpr int G = lg_bits(LW);
@@ -257,21 +276,35 @@ LDEV void enc16n_body(const EncArgs& a) {
     uint64_t pp[TL::NR];
     lane_ptrs(pp, a.out, [&](int r) { return min(TL::piece(0, r, w), a.R - 1); });
     if (!cl.live) return;
+    if constexpr (kVerify) {
+        // branch-free: a register past R holds piece R - 1's address and is not flagged
+#pragma unroll
+        for (int r = 0; r < TL::NR; ++r) ld_unit(x[r], reinterpret_cast<const uint8_t*>(pp[r]), cl.off);
+#pragma unroll
+        for (int r = 0; r < TL::NR; ++r) {
+            const unsigned tp = TL::piece(0, r, w);
+            uint32_t d = 0;
+#pragma unroll
+            for (int k = 0; k < TL::U; ++k) d |= x[r][k] ^ acc[r][k];
+            flag_piece<LW>(a.report, tp, tp < a.R && d != 0);
+        }
+        return;
+    }
 #pragma unroll
     for (int r = 0; r < TL::NR; ++r)
         if (TL::piece(0, r, w) < a.R) st_unit(reinterpret_cast<uint8_t*>(pp[r]), cl.off, acc[r]);
     STAMP16(7);
 }
 
-template <int T, int R, int LW>
+template <int T, int R, int LW, bool kVerify = false>
 __global__ void __launch_bounds__((threads_n<T, R, LW>()), 4) k_enc16n(EncArgs a) {
-    enc16n_body<T, R, LW>(a);
+    enc16n_body<T, R, LW, kVerify>(a);
 }
 // Batched launch (leo_amd_encode_batch): object blockIdx.y of an array of
 // argument blocks in device memory, one grid over every object's strips.
-template <int T, int R, int LW>
+template <int T, int R, int LW, bool kVerify = false>
 __global__ void __launch_bounds__((threads_n<T, R, LW>()), 4) k_enc16n_batch(const EncArgs* __restrict__ objs) {
-    enc16n_body<T, R, LW>(objs[blockIdx.y]);
+    enc16n_body<T, R, LW, kVerify>(objs[blockIdx.y]);
 }
 
 // Chunk-parallel form of enc16n_body for single calls on few column strips
@@ -359,17 +392,17 @@ __global__ void __launch_bounds__((threads_n<T, R, LW>()), 4) k_enc16n_comb(EncA
         if (TL::piece(0, r, w) < a.R) st_unit(reinterpret_cast<uint8_t*>(pp[r]), cl.off, acc[r]);
 }
 
-template <int T, int R, int LW>
+template <int T, int R, int LW, bool kVerify = false>
 hipError_t launch_enc16n(const EncArgs& a, hipStream_t s) {
     using TL = Tile<FF16, T, R, 1, LW, 0, lg_bits(LW)>;
     constexpr size_t lds = (TL::kXchDwords + 2 * tab16_set_dwords(T)) * 4;
     static_assert(lds <= (LW == 16 ? 80 : 160) * 1024, "two (16-unit strips) / one workgroup(s) per CU");
-    static hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_enc16n<T, R, LW>),
+    static hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_enc16n<T, R, LW, kVerify>),
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
     if (attr != hipSuccess) return attr;
     void* params[] = {const_cast<EncArgs*>(&a)};
     const unsigned grid = unsigned((a.nunits + LW - 1) / LW);
-    return hipLaunchKernel(reinterpret_cast<const void*>(&k_enc16n<T, R, LW>), dim3(grid), dim3(threads_n<T, R, LW>()),
+    return hipLaunchKernel(reinterpret_cast<const void*>(&k_enc16n<T, R, LW, kVerify>), dim3(grid), dim3(threads_n<T, R, LW>()),
                            params, lds, s);
 }
 
@@ -1045,6 +1078,15 @@ hipError_t launch_encode16_small(unsigned Tm, const EncArgs& a, hipStream_t s) {
         default: return hipErrorInvalidValue;
     }
 }
+// The verify form with its arguments by value exists for m = 256 only: for
+// m = 128 it compiled to 12 (32-unit strips) and 20 (16-unit strips) bytes of
+// scratch a lane at 128 VGPRs, whatever the shape of its epilogue, where the
+// form that reads its arguments from device memory (k_enc16n_batch) takes 124
+// VGPRs and none.  A single m = 128 call runs that one, as a batch of one.
+bool verify16_small_by_value(unsigned Tm) { return Tm == 8; }
+hipError_t launch_verify16_small(unsigned Tm, const EncArgs& a, hipStream_t s) {
+    return Tm == 8 ? launch_enc16n<8, 3, 16, true>(a, s) : hipErrorInvalidValue;
+}
 
 // The chunk-parallel form (k_enc16n_part + k_enc16n_comb, 16-unit strips) for
 // single calls with several chunks on fewer 16-unit strips than CUs; the slab
@@ -1086,7 +1128,7 @@ hipError_t launch_encode16_split(unsigned Tm, const EncArgs& a, hipStream_t s) {
 
 // Batches of `count` objects of one shape: argument blocks in device memory.
 hipError_t launch_encode16_small_batch(unsigned Tm, const EncArgs* objs, unsigned count, uint64_t nunits,
-                                       hipStream_t s) {
+                                       hipStream_t s, bool verify) {
     auto go = [&](auto fn, unsigned threads, size_t lds) {
         const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(fn),
                                                     hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
@@ -1099,8 +1141,12 @@ hipError_t launch_encode16_small_batch(unsigned Tm, const EncArgs* objs, unsigne
     using TL7 = Tile<FF16, 7, 3, 1, 16, 0, lg_bits(16)>;
     using TL8 = Tile<FF16, 8, 3, 1, 16, 0, lg_bits(16)>;
     switch (Tm) {
-        case 7: return go(&k_enc16n_batch<7, 3, 16>, threads_n<7, 3, 16>(), (TL7::kXchDwords + 2 * tab16_set_dwords(7)) * 4);
-        case 8: return go(&k_enc16n_batch<8, 3, 16>, threads_n<8, 3, 16>(), (TL8::kXchDwords + 2 * tab16_set_dwords(8)) * 4);
+        case 7:
+            return verify ? go(&k_enc16n_batch<7, 3, 16, true>, threads_n<7, 3, 16>(), (TL7::kXchDwords + 2 * tab16_set_dwords(7)) * 4)
+                          : go(&k_enc16n_batch<7, 3, 16>, threads_n<7, 3, 16>(), (TL7::kXchDwords + 2 * tab16_set_dwords(7)) * 4);
+        case 8:
+            return verify ? go(&k_enc16n_batch<8, 3, 16, true>, threads_n<8, 3, 16>(), (TL8::kXchDwords + 2 * tab16_set_dwords(8)) * 4)
+                          : go(&k_enc16n_batch<8, 3, 16>, threads_n<8, 3, 16>(), (TL8::kXchDwords + 2 * tab16_set_dwords(8)) * 4);
         default: return hipErrorInvalidValue;
     }
 }

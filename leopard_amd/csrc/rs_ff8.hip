@@ -226,8 +226,20 @@ LDEV auto lane_pred(const P& p) {
 // tests compile away (they were a third of the kernel's scalar instructions).
 // kFormDenseDec = the same tile run as the inverse map, the full-loss decode of
 // a K = R = m code (see launch_ff8_decode_full).
-template <int T, int RB, bool kMulti, int NA, int G, int kForm = kFormGeneral, class A = Ff8EncArgs>
+// kForm | kFormVerify = the verify form of the general and dense encode tiles
+// (leo_amd_verify): the same transforms, and in place of the stores the stored
+// recovery dwords are loaded from the addresses the stores would have used,
+// XORed with the computed values, and a wave that sees a difference in piece
+// tp ORs bit tp into the object's report.  A register holds one piece per
+// wave (G = 0: the piece number is wave-uniform), so the flag is per register
+// and the ballot over the wave's live lanes blames the right piece.  A piece
+// with a zero pointer (pointer-table blocks) is not checked.  No store at all
+// on a clean stripe.
+template <int T, int RB, bool kMulti, int NA, int G, int kFormV = kFormGeneral, class A = Ff8EncArgs>
 LDEV void ff8_enc(const A& a) {
+    constexpr int kForm = kFormV & ~kFormVerify;
+    constexpr bool kVerify = (kFormV & kFormVerify) != 0;
+    static_assert(!kVerify || (G == 0 && kForm != kFormDenseDec), "verify forms: encode tiles without lane groups");
     constexpr bool kDense = kForm != kFormGeneral;
     static_assert(!(kDense && kMulti), "dense = one chunk");
     if constexpr ((LAMD_ABLATE & 16) != 0) return;
@@ -361,6 +373,27 @@ LDEV void ff8_enc(const A& a) {
         for (int r = 0; r < TL::NR; ++r) pp[r] = a.out_piece(TL::piece(0, r, w)) + cl.base;  // tp < m: R + tp < 256
     }
     if (!cl.live) return;
+    if constexpr (kVerify) {
+        // which of this wave's pieces are checked (wave-uniform)
+        bool chk[TL::NR];
+#pragma unroll
+        for (int r = 0; r < TL::NR; ++r) {
+            chk[r] = kDense || TL::piece(0, r, w) < a.R;
+            if constexpr (!A::kSlab) chk[r] = chk[r] && po[r] != 0;
+        }
+        uint32_t v[TL::NR];
+#pragma unroll
+        for (int r = 0; r < TL::NR; ++r) v[r] = chk[r] ? gload_at(pp[r], cl) : x[r][0];
+#pragma unroll
+        for (int r = 0; r < TL::NR; ++r) {
+            const uint64_t bad = __builtin_amdgcn_ballot_w64(v[r] != x[r][0]);
+            if (bad != 0 && (threadIdx.x & 63u) == unsigned(__builtin_ctzll(bad))) {
+                const unsigned tp = TL::piece(0, r, w);
+                atomicOr(a.report + (tp >> 5), 1u << (tp & 31u));
+            }
+        }
+        return;
+    }
 #pragma unroll
     for (int r = 0; r < TL::NR; ++r) {
         const unsigned tp = TL::piece(0, r, w);
@@ -826,35 +859,40 @@ inline bool enc_dense(unsigned T, const Ff8EncArgs& a) {
     return a.nchunks == 1 && a.K == (1u << T) && a.R == (1u << T);
 }
 
-template <int T, int RB, int NA, int G>
+// V: the verify forms (leo_amd_verify; lane groups G = 0 only, tags 8 / 12)
+template <int T, int RB, int NA, int G, bool V = false>
 hipError_t enc_RBG(const Ff8EncArgs& a, hipStream_t s) {
     constexpr size_t lds = areas8(NA) * (tile_dwords_for(T, RB) >> G) + LdsTab8<256>::kDwords;
     constexpr unsigned threads = threads_for(T, RB) >> G;
+    constexpr int kV = V ? kFormVerify : 0;
+    static_assert(!V || G == 0, "verify forms have no lane groups");
     if constexpr (G == 0)
         if (enc_dense(T, a))
-            return launch8<EncTag<T, RB, false, NA, 4>>(&k_ff8_enc<T, RB, false, NA, 0, kFormDenseEnc>, threads, a, lds,
-                                                         s);
+            return launch8<EncTag<T, RB, false, NA, V ? 12 : 4>>(&k_ff8_enc<T, RB, false, NA, 0, kFormDenseEnc | kV>,
+                                                                  threads, a, lds, s);
     if (a.nchunks > 1)
-        return launch8<EncTag<T, RB, true, NA, G>>(&k_ff8_enc<T, RB, true, NA, G>, threads, a, lds, s, 64u >> G);
-    return launch8<EncTag<T, RB, false, NA, G>>(&k_ff8_enc<T, RB, false, NA, G>, threads, a, lds, s, 64u >> G);
+        return launch8<EncTag<T, RB, true, NA, V ? 8 : G>>(&k_ff8_enc<T, RB, true, NA, G, kV>, threads, a, lds, s,
+                                                            64u >> G);
+    return launch8<EncTag<T, RB, false, NA, V ? 8 : G>>(&k_ff8_enc<T, RB, false, NA, G, kV>, threads, a, lds, s,
+                                                         64u >> G);
 }
-template <int T, int RB, int NA>
+template <int T, int RB, int NA, bool V = false>
 hipError_t enc_RB(const Ff8EncArgs& a, hipStream_t s) {
-    if constexpr (NA == 1 && T - RB >= 2 && T > RB) {
+    if constexpr (!V && NA == 1 && T - RB >= 2 && T > RB) {
         const int g = enc_lane_groups(a.nunits);
         if (g == 2) return enc_RBG<T, RB, NA, 2>(a, s);
         if (g == 1) return enc_RBG<T, RB, NA, 1>(a, s);
     }
-    return enc_RBG<T, RB, NA, 0>(a, s);
+    return enc_RBG<T, RB, NA, 0, V>(a, s);
 }
-template <int T>
+template <int T, bool V = false>
 hipError_t enc_T(const Ff8EncArgs& a, hipStream_t s) {
     // wide form once every CU gets >= 4 strips (256 CUs x 4 x 256 B: 256 KiB pieces)
     if constexpr (wide_bits8(T) != reg_bits8(T))
-        if (a.nunits >= 65536 || force_wide()) return enc_RB<T, wide_bits8(T), 1>(a, s);
+        if (a.nunits >= 65536 || force_wide()) return enc_RB<T, wide_bits8(T), 1, V>(a, s);
     if constexpr (kPipe8)
-        if (a.nunits <= kOneWgPerCuUnits) return enc_RB<T, reg_bits8(T), 2>(a, s);
-    return enc_RB<T, reg_bits8(T), 1>(a, s);
+        if (a.nunits <= kOneWgPerCuUnits) return enc_RB<T, reg_bits8(T), 2, V>(a, s);
+    return enc_RB<T, reg_bits8(T), 1, V>(a, s);
 }
 template <int T, int RB, int NA>
 hipError_t dec_RB(const Ff8DecArgs& a, hipStream_t s) {
@@ -908,6 +946,15 @@ hipError_t launch_ff8_encode(unsigned T, const Ff8EncArgs& a, hipStream_t s) {
     hipError_t e = hipErrorInvalidValue;
     static_for<1, 8>([&](auto I) {
         if (T == unsigned(decltype(I)::value)) e = enc_T<decltype(I)::value>(a, s);
+    });
+    return e;
+}
+
+// The verify form of the same tile selection (a.report: the object's bitmap).
+hipError_t launch_ff8_verify(unsigned T, const Ff8EncArgs& a, hipStream_t s) {
+    hipError_t e = hipErrorInvalidValue;
+    static_for<1, 8>([&](auto I) {
+        if (T == unsigned(decltype(I)::value)) e = enc_T<decltype(I)::value, true>(a, s);
     });
     return e;
 }
@@ -966,7 +1013,16 @@ hipError_t launch_ff8_encode_batch(unsigned T, const Ff8EncArgs* objs, unsigned 
         constexpr int TT = decltype(I)::value, RB = batch_bits8(TT);
         constexpr size_t lds = tile_dwords_for(TT, RB) + LdsTab8<256>::kDwords;
         if (T != unsigned(TT)) return;
-        if (form == kFormDenseEnc)
+        if (form == (kFormDenseEnc | kFormVerify))
+            e = launch8_batch<EncBatchTag<TT + 80, false>>(&k_ff8_enc_batch<TT, RB, false, kFormDenseEnc | kFormVerify>,
+                                                           threads_for(TT, RB), objs, count, nunits, lds, s);
+        else if (form == kFormVerify && multi)
+            e = launch8_batch<EncBatchTag<TT + 64, true>>(&k_ff8_enc_batch<TT, RB, true, kFormVerify>,
+                                                          threads_for(TT, RB), objs, count, nunits, lds, s);
+        else if (form == kFormVerify)
+            e = launch8_batch<EncBatchTag<TT + 64, false>>(&k_ff8_enc_batch<TT, RB, false, kFormVerify>,
+                                                           threads_for(TT, RB), objs, count, nunits, lds, s);
+        else if (form == kFormDenseEnc)
             e = launch8_batch<EncBatchTag<TT + 16, false>>(&k_ff8_enc_batch<TT, RB, false, kFormDenseEnc>,
                                                            threads_for(TT, RB), objs, count, nunits, lds, s);
         else if (form == kFormDenseDec)
@@ -985,14 +1041,19 @@ hipError_t launch_ff8_encode_batch(unsigned T, const Ff8EncArgs* objs, unsigned 
 hipError_t launch_ff8_encode_slab(unsigned T, const Ff8SlabBatch& b, unsigned count, bool multi, int form,
                                   hipStream_t s, unsigned cus, uint32_t* q, uint32_t* qclear) {
     // dense 128 + 128 forms: the bit-sliced tile (rs_ff8_bs.hip)
-    if (form != kFormGeneral && !multi && bs_tile_enabled() && ff8_bs_supported(T, b.K, b.R, b.nchunks))
+    if ((form & ~kFormVerify) != kFormGeneral && !multi && bs_tile_enabled() && ff8_bs_supported(T, b.K, b.R, b.nchunks))
         return launch_ff8_bs_slab(b, count, form, s, cus, q, qclear);
     hipError_t e = hipErrorInvalidValue;
     static_for<1, 8>([&](auto I) {
         constexpr int TT = decltype(I)::value, RB = batch_bits8(TT);
         constexpr size_t lds = (tile_dwords_for(TT, RB) + LdsTab8<256>::kDwords) * 4;
         if (T != unsigned(TT)) return;
-        const void* fn = form == kFormDenseEnc   ? reinterpret_cast<const void*>(&k_ff8_enc_slab<TT, RB, false, kFormDenseEnc>)
+        constexpr int kDV = kFormDenseEnc | kFormVerify;
+        const void* fn = form == kDV ? reinterpret_cast<const void*>(&k_ff8_enc_slab<TT, RB, false, kDV>)
+                         : form == kFormVerify
+                             ? (multi ? reinterpret_cast<const void*>(&k_ff8_enc_slab<TT, RB, true, kFormVerify>)
+                                      : reinterpret_cast<const void*>(&k_ff8_enc_slab<TT, RB, false, kFormVerify>))
+                         : form == kFormDenseEnc ? reinterpret_cast<const void*>(&k_ff8_enc_slab<TT, RB, false, kFormDenseEnc>)
                          : form == kFormDenseDec ? reinterpret_cast<const void*>(&k_ff8_enc_slab<TT, RB, false, kFormDenseDec>)
                          : multi                 ? reinterpret_cast<const void*>(&k_ff8_enc_slab<TT, RB, true>)
                                                  : reinterpret_cast<const void*>(&k_ff8_enc_slab<TT, RB, false>);

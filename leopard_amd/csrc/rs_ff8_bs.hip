@@ -528,6 +528,64 @@ LDEV void store_half(const Reg& x, const BsTile<kNarrow>& T) {
 #endif
     }
 }
+// The verify form's epilogue (leo_amd_verify), verify_issue then verify_check
+// in place of store_half: the
+// stored recovery segments are loaded from the addresses the stores would have
+// used (a segment past the piece's end: segment 0, which this lane then holds
+// the output of, as in store_half -- no branch), XORed with the computed
+// values, and a lane group that sees a difference in piece pg | r ORs that
+// piece's bit into the object's report `rep`.  The 8 << WB lanes of a lane
+// group hold the same 16 pieces, other lane groups of the wave hold others: the
+// wave's ballot is cut into lane groups and the first flagged lane of a group
+// reports for it.  Nothing is written on a clean stripe.
+//
+// The stored segments of one half (8 registers x 2 segments of 16 bytes), all in
+// flight together: one exposed load latency per half.  They are issued behind
+// the half's transposes: issued ahead of them (to run under them) the
+// cooperative tile spilled 28 VGPRs at LAMD_BS_OCC = 2; here it holds 247
+// against the encode tile's 240.
+struct BsStored {
+    v4u s0[8], s1[8];
+};
+template <int R0, bool kNarrow>
+LDEV void verify_issue(BsStored& st, const BsTile<kNarrow>& T) {
+    bs_fence();  // the loads stay here: not hoisted into the butterflies, not sunk to their use
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const uint64_t base = T.out + uint64_t(int64_t(R0 + i) * T.out_stride);
+#if LAMD_BS_NT & 1
+        st.s0[i] = __builtin_nontemporal_load(bs_addr(base, T.out0));
+        st.s1[i] = __builtin_nontemporal_load(bs_addr(base, T.out1));
+#else
+        st.s0[i] = *bs_addr(base, T.out0);
+        st.s1[i] = *bs_addr(base, T.out1);
+#endif
+    }
+    bs_fence();
+}
+template <int R0, int WB>
+LDEV void verify_check(const Reg& x, const BsStored& st, uint32_t* rep, unsigned g) {
+    constexpr unsigned kGroup = 8u << WB;
+    const unsigned lane = threadIdx.x & 63u;
+    const unsigned first = lane & ~(kGroup - 1u);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const int r = R0 + i;
+        const v4u &a = st.s0[i], &b = st.s1[i];
+        const uint32_t d = (x[r][0] ^ a.x) | (x[r][1] ^ a.y) | (x[r][2] ^ a.z) | (x[r][3] ^ a.w) |
+                           (x[r][4] ^ b.x) | (x[r][5] ^ b.y) | (x[r][6] ^ b.z) | (x[r][7] ^ b.w);
+        const uint64_t bad = __builtin_amdgcn_ballot_w64(d != 0);
+        const uint64_t mine = (bad >> first) & ((uint64_t(1) << kGroup) - 1u);
+        if (mine != 0 && lane == first + unsigned(__builtin_ctzll(mine))) {
+            // (computed here, on the rare path: as loop invariants the 16 pieces' bits took 16 VGPRs)
+            unsigned gg = g;
+            asm volatile("" : "+v"(gg));
+            const unsigned p = piece_of(kLay0, unsigned(r), gg);
+            atomicOr(rep + (p >> 5), 1u << (p & 31u));
+        }
+    }
+    bs_fence();
+}
 template <int R0>
 LDEV void transpose_half(Reg& x, const XMasks& xm) {
 #pragma unroll
@@ -609,9 +667,15 @@ LDEV void low_layers_of(Reg& x, const uint32_t (&G)[3], unsigned wv) {
 // through LDS, every wave reads the same word, so all of them take the same
 // next tile or leave together -- no wave may return or loop alone, the others
 // would wait at a barrier for ever.
-template <int kForm, bool kNarrow, int WB = 0>
+//
+// kFormV = kFormDenseEnc | kFormVerify: the verify form (verify_issue / verify_check in place of
+// store_half; object obj's report at b.report + 4 obj).
+template <int kFormV, bool kNarrow, int WB = 0>
 __global__ void __launch_bounds__(WB ? (64 << WB) : 64 * kBsWaves) __attribute__((amdgpu_waves_per_eu(LAMD_BS_OCC, LAMD_BS_OCC)))
 k_ff8_bs_slab(Ff8SlabBatch b, uint32_t count, uint32_t strips, uint32_t* q, uint32_t* qclear) {
+    constexpr int kForm = kFormV & ~kFormVerify;
+    constexpr bool kVerify = (kFormV & kFormVerify) != 0;
+    static_assert(!kVerify || kForm == kFormDenseEnc, "the verify form of the dense encode tile");
     constexpr int kOffI = kForm == kFormDenseDec ? -1 : 127;  // IFFT skew base
     constexpr int kOffF = kForm == kFormDenseDec ? 127 : -1;  // FFT skew base
     constexpr unsigned kTiles = WB ? 1u : unsigned(kBsWaves);  // tiles in flight per workgroup
@@ -692,17 +756,24 @@ k_ff8_bs_slab(Ff8SlabBatch b, uint32_t count, uint32_t strips, uint32_t* q, uint
         const unsigned tn = head != nullptr ? n + xq + 8u * __builtin_amdgcn_readfirstlane(kq) : t + n;
         const bool more = tn < total;
         const BsTile<kNarrow> nxt = bs_tile<kNarrow, WB>(b, more ? tn : t, strips, g, l);
+        [[maybe_unused]] BsStored stored;  // verify form
+        uint32_t* rep = nullptr;           // verify form: the report of the current tile's object (128 pieces: 4 words)
+        if constexpr (kVerify) rep = b.report + size_t(t / strips) * 4u;
 #ifndef ABL_ARITH
         low_layers_of<false, kOffF, 0, WB>(x, G, wv);
         transpose_half<0>(x, xm);
 #endif
-        store_half<0>(x, cur);
+        if constexpr (kVerify) verify_issue<0>(stored, cur);
+        if constexpr (kVerify) verify_check<0, WB>(x, stored, rep, g);
+        else store_half<0>(x, cur);
         if (more) load_half<0, 8>(x, nxt);
 #ifndef ABL_ARITH
         low_layers_of<false, kOffF, 1, WB>(x, G, wv);
         transpose_half<8>(x, xm);
 #endif
-        store_half<8>(x, cur);
+        if constexpr (kVerify) verify_issue<8>(stored, cur);
+        if constexpr (kVerify) verify_check<8, WB>(x, stored, rep, g);
+        else store_half<8>(x, cur);
         if (!more) break;
         load_half<8, 16>(x, nxt);
         t = tn;
@@ -764,7 +835,9 @@ hipError_t launch_ff8_bs_slab(const Ff8SlabBatch& b, unsigned count, int form, h
                               uint32_t* q, uint32_t* qclear) {
     if (count == 0 || count > kSlabObjs || (b.nunits * 4u) % 64u != 0 || b.K != 128 || b.R != 128)
         return hipErrorInvalidValue;
-    if (form != kFormDenseEnc && form != kFormDenseDec) return hipErrorInvalidValue;
+    constexpr int kVer = kFormDenseEnc | kFormVerify;
+    if (form != kFormDenseEnc && form != kFormDenseDec && form != kVer) return hipErrorInvalidValue;
+    if (form == kVer && b.report == nullptr) return hipErrorInvalidValue;
     cus = std::max(cus, 1u);
     // 32-bit lane offsets when every slab's lane offsets (up to 127 strides + a
     // strip) fit them; the cooperative tile is built for those only
@@ -794,7 +867,12 @@ hipError_t launch_ff8_bs_slab(const Ff8SlabBatch& b, unsigned count, int form, h
     void* params[] = {const_cast<Ff8SlabBatch*>(&b), &cnt, &strips, &q, &qclear};
     const bool dec = form == kFormDenseDec;
     const void* fn = nullptr;
-    if (wb == 2)
+    if (form == kVer)
+        fn = wb == 2   ? bs_kernel_wg<kVer, 2>()
+             : wb == 1 ? bs_kernel_wg<kVer, 1>()
+             : narrow  ? reinterpret_cast<const void*>(&k_ff8_bs_slab<kVer, true>)
+                       : reinterpret_cast<const void*>(&k_ff8_bs_slab<kVer, false>);
+    else if (wb == 2)
         fn = dec ? bs_kernel_wg<kFormDenseDec, 2>() : bs_kernel_wg<kFormDenseEnc, 2>();
     else if (wb == 1)
         fn = dec ? bs_kernel_wg<kFormDenseDec, 1>() : bs_kernel_wg<kFormDenseEnc, 1>();

@@ -94,6 +94,14 @@ LDEV void ld16z(uint32_t* x, const PieceMap& pm, bool ok, unsigned i, const uint
     ld16(x, base, c.off);
 }
 
+// Verify forms (leo_amd_verify): every lane of the wave holds piece tp (wave-
+// uniform); where a live lane saw a difference, one lane ORs the piece's bit
+// into the object's report.  No write on a clean piece.
+LDEV void flag_piece(uint32_t* report, unsigned tp, bool diff) {
+    const uint64_t bad = __builtin_amdgcn_ballot_w64(diff);
+    if (bad != 0 && (threadIdx.x & 63u) == unsigned(__builtin_ctzll(bad))) atomicOr(report + (tp >> 5), 1u << (tp & 31u));
+}
+
 // Strip addresses of the pieces of a caller's piece map (a pointer table or a
 // slab, wave-uniform) that a lane's registers r < NR hold, `ok(r)` false: the
 // zero page.  The table-or-slab test is made once for all of them, the table
@@ -139,7 +147,11 @@ LDEV void load_or_zero(uint32_t* x, const PieceMap& pm, bool ok, unsigned i, con
 
 // ------------------------------------------------------------------ encode --
 
-template <class F, int T>
+// kVerify: the verify form (leo_amd_verify).  a.out holds the stored recovery
+// pieces; in place of the stores they are loaded from the same addresses (into
+// the chunk registers, free by then), XORed with the computed values and
+// flagged per piece in a.report.  Nothing is written on a clean stripe.
+template <class F, int T, bool kVerify = false>
 __global__ void __launch_bounds__(64 << wave_bits(T), 4) k_enc_fused(EncArgs a) {
     if constexpr ((LAMD_ABLATE & 16) != 0) return;
     using TL = Tile<F, T, reg_bits(T), C>;
@@ -181,6 +193,23 @@ __global__ void __launch_bounds__(64 << wave_bits(T), 4) k_enc_fused(EncArgs a) 
     win.stage(a.sktab, -1);
     TL::template fft<true>(acc, w, lane, lds, ps, win, BelowLive{a.R});
     TL::pin(acc);
+    if constexpr (kVerify) {
+        // branch-free loads: a register past R re-reads piece R - 1 and is not flagged
+#pragma unroll
+        for (int r = 0; r < TL::NR; ++r) {
+            const unsigned tp = TL::piece(0, r, w);
+            load_units<F, C>(x[r], a.out.ptr(tp < a.R ? tp : a.R - 1), ql);
+        }
+#pragma unroll
+        for (int r = 0; r < TL::NR; ++r) {
+            const unsigned tp = TL::piece(0, r, w);
+            uint32_t d = 0;
+#pragma unroll
+            for (int k = 0; k < TL::U; ++k) d |= x[r][k] ^ acc[r][k];
+            if (tp < a.R) flag_piece(a.report, tp, live && d != 0);
+        }
+        return;
+    }
 #pragma unroll
     for (int r = 0; r < TL::NR; ++r) {
         const unsigned tp = TL::piece(0, r, w);
@@ -357,7 +386,10 @@ __global__ void __launch_bounds__(threads16(T, R), LAMD_HI_WAVES) k_enc_hi(EncAr
 
 // pass 3: FFT over the low bits, keep outputs g < R.  When m = 2^kLoBits (no
 // high pass) the chunk IFFTs of pass 1 are combined here: x = XOR_c U[c*m + g].
-template <int R, int S>
+// kVerify: the verify form (leo_amd_verify): a.out holds the stored pieces,
+// loaded in batches of 8 where the encoder stores, compared and flagged per
+// piece in a.report; nothing is written on a clean stripe.
+template <int R, int S, bool kVerify = false>
 __global__ void __launch_bounds__(threads16(kLoBits, R), 4) k_enc_fin(EncArgs a) {
     constexpr int T = kLoBits;
     constexpr int NT = threads16(T, R);
@@ -382,6 +414,27 @@ __global__ void __launch_bounds__(threads16(kLoBits, R), 4) k_enc_fin(EncArgs a)
             xor_load<TL, TL::kLast>(x, a.slab_in, [&](unsigned tp) { return (c << T) + pos(tp); }, w, cl);
     TL::fft(x, w, lane, lds, ps, LdsWindow16{set, y << T, 0}, prune16(BelowLive{a.R}));
     if (!live) return;
+    if constexpr (kVerify) {
+        constexpr int B = TL::NR < 8 ? TL::NR : 8;
+        static_for<0, TL::NR / B>([&](auto BI) {
+            constexpr int r0 = decltype(BI)::value * B;
+            uint32_t v[B][TL::U];
+            // branch-free loads: a register past R re-reads piece R - 1 and is not flagged
+            static_for<0, B>([&](auto I) {
+                const unsigned g = ps.global(TL::piece(0, r0 + I.value, w));
+                ld16(v[I.value], a.out.ptr(g < a.R ? g : a.R - 1) + cl.strip, cl.off);
+            });
+            __builtin_amdgcn_sched_barrier(0);  // one batch of loads in flight at a time
+            static_for<0, B>([&](auto I) {
+                const unsigned g = ps.global(TL::piece(0, r0 + I.value, w));
+                uint32_t d = 0;
+#pragma unroll
+                for (int k = 0; k < TL::U; ++k) d |= v[I.value][k] ^ x[r0 + I.value][k];
+                if (g < a.R) flag_piece(a.report, g, d != 0);
+            });
+        });
+        return;
+    }
 #pragma unroll
     for (int r = 0; r < TL::NR; ++r) {
         const unsigned g = ps.global(TL::piece(0, r, w));
@@ -744,10 +797,10 @@ constexpr size_t full_tile_lds() {  // transpose area + staged skew tables
     return tile_lds_dwords<F, T>() + SkewTables<F, (64 << wave_bits(T))>::kLdsDwords;
 }
 
-template <class F, int T>
+template <class F, int T, bool kVerify = false>
 struct EncFusedFn {
     static hipError_t run(const EncArgs& a, hipStream_t s) {
-        return launch(&k_enc_fused<F, T>, dim3(tiles_for(a.nunits)), 64u << wave_bits(T), full_tile_lds<F, T>(), s,
+        return launch(&k_enc_fused<F, T, kVerify>, dim3(tiles_for(a.nunits)), 64u << wave_bits(T), full_tile_lds<F, T>(), s,
                       &a);
     }
 };
@@ -801,6 +854,13 @@ hipError_t launch_encode_fused16(unsigned T, const EncArgs& a, hipStream_t s) {
     });
     return e;
 }
+hipError_t launch_verify_fused16(unsigned T, const EncArgs& a, hipStream_t s) {
+    hipError_t e = hipErrorInvalidValue;
+    static_for<1, 9>([&](auto I) {
+        if (T == unsigned(decltype(I)::value)) e = EncFusedFn<FF16, decltype(I)::value, true>::run(a, s);
+    });
+    return e;
+}
 hipError_t launch_encode_lo(const EncArgs& a, hipStream_t s) {
     const unsigned m = 1u << a.Tm;
     return launch(&k_enc_lo<kLoR, kLoS>, dim3(tiles_for(a.nunits), m >> kLoBits, a.nchunks),
@@ -810,7 +870,8 @@ hipError_t launch_encode_hi(const EncArgs& a, hipStream_t s) {
     if (a.nchunks > 1) return dispatch_T<EncHiMulti, 1, 6>(a.Tm - kLoBits, a, s);
     return dispatch_T<EncHiSingle, 1, 7>(a.Tm - kLoBits, a, s);
 }
-hipError_t launch_encode_fin(const EncArgs& a, hipStream_t s) {
+template <bool kVerify>
+hipError_t launch_fin(const EncArgs& a, hipStream_t s) {
     const unsigned tiles = (a.R + (1u << kLoBits) - 1) >> kLoBits;
     const dim3 grid(tiles_for(a.nunits), tiles);
     // A grid of at most one workgroup per CU (e.g. R <= 256 on 64 KiB pieces):
@@ -818,10 +879,12 @@ hipError_t launch_encode_fin(const EncArgs& a, hipStream_t s) {
     // workgroup per CU) halve every wave's work where the 32-piece form would
     // leave 3 of 4 wave slots of each SIMD empty.
     if (grid.x * grid.y <= kNarrowGrid)
-        return launch(&k_enc_fin<4, 0>, grid, threads16(kLoBits, 4), lds16_dwords<kLoBits, 4, 0>(1, 0), s, &a);
-    return launch(&k_enc_fin<kLoR, kLoS>, grid, threads16(kLoBits, kLoR), lds16_dwords<kLoBits, kLoR, kLoS>(1, 0), s,
-                  &a);
+        return launch(&k_enc_fin<4, 0, kVerify>, grid, threads16(kLoBits, 4), lds16_dwords<kLoBits, 4, 0>(1, 0), s, &a);
+    return launch(&k_enc_fin<kLoR, kLoS, kVerify>, grid, threads16(kLoBits, kLoR),
+                  lds16_dwords<kLoBits, kLoR, kLoS>(1, 0), s, &a);
 }
+hipError_t launch_encode_fin(const EncArgs& a, hipStream_t s) { return launch_fin<false>(a, s); }
+hipError_t launch_verify_fin(const EncArgs& a, hipStream_t s) { return launch_fin<true>(a, s); }
 hipError_t launch_decode_lo(const DecArgs& a, hipStream_t s) {
     return launch(&k_dec_lo<kLoR, kLoS>, dim3(tiles_for(a.nunits), a.nlo), threads16(kLoBits, kLoR),
                   lds16_dwords<kLoBits, kLoR, kLoS>(1, 1 << kLoBits), s, &a);
