@@ -2163,6 +2163,15 @@ LeopardResult missing_output(void* const* outs, unsigned count, const void* cons
     return Leopard_Success;
 }
 
+// The first non-null piece decides the device of a decode call.
+const void* first_piece(unsigned K, unsigned R, const void* const* orig, const void* const* rec) {
+    for (unsigned i = 0; i < K; ++i)
+        if (orig[i]) return orig[i];
+    for (unsigned i = 0; i < R; ++i)
+        if (rec[i]) return rec[i];
+    return nullptr;
+}
+
 LeopardResult encode_any(uint64_t bytes, uint64_t off, unsigned K, unsigned R, const void* const* orig, void** work) {
     MemKind kind;
     const int dev = pick_device(orig[0], &kind);
@@ -2239,9 +2248,7 @@ LeopardResult decode_any(uint64_t bytes, uint64_t off, unsigned K, unsigned R, c
         if (rec[i]) { ++got; got_i = i; }
     if (got < lost) return Leopard_NeedMoreData;  // leopard.cpp:275-276
 
-    const void* first = nullptr;
-    for (unsigned i = 0; i < K && !first; ++i) first = orig[i];
-    for (unsigned i = 0; i < R && !first; ++i) first = rec[i];
+    const void* first = first_piece(K, R, orig, rec);
     if (!first) first = work[0];
     MemKind kind;
     const int dev = pick_device(first, &kind);
@@ -2356,6 +2363,10 @@ LeopardResult decode_any(uint64_t bytes, uint64_t off, unsigned K, unsigned R, c
     r = run_host_pipeline(c, bytes, hin, hout, slice_fn);
     if (r != Leopard_Success) return r;
     return finish(c, true);
+}
+
+bool check_slice(uint64_t buffer_bytes, uint64_t off, uint64_t bytes) {  // whole 64-byte blocks inside the pieces
+    return bytes != 0 && bytes % 64 == 0 && off % 64 == 0 && off + bytes <= buffer_bytes;
 }
 
 // Validation shared by leo_encode / leo_amd_encode_slice (leopard.cpp:131-140, 162-166).
@@ -3052,12 +3063,8 @@ LeopardResult decode_batch(unsigned count, uint64_t bytes, unsigned K, unsigned 
     const unsigned m = next_pow2(R), n = next_pow2(m + K);
     MemKind kind = MemKind::Host;
     int dev = -1;
-    if (general && n <= 256 && bytes <= kFf8MaxLaunchBytes) {
-        const void* first = nullptr;  // the device rule of decode_any
-        for (unsigned i = 0; i < K && !first; ++i) first = orig[0][i];
-        for (unsigned i = 0; i < R && !first; ++i) first = rec[0][i];
-        dev = pick_device(first, &kind);
-    }
+    if (general && n <= 256 && bytes <= kFf8MaxLaunchBytes)
+        dev = pick_device(first_piece(K, R, orig[0], rec[0]), &kind);  // the device rule of decode_any
     if (kind == MemKind::Device) {
         const unsigned Tn = log2u(n);
         bool full = true;  // every object a full loss of a K = R = m code: the inverse encoder tile
@@ -3114,11 +3121,8 @@ LeopardResult decode_batch(unsigned count, uint64_t bytes, unsigned K, unsigned 
         }
     }
     if (general && narrow_decode16(K, R, bytes)) {
-        const void* first = nullptr;  // the device rule of decode_any
-        for (unsigned i = 0; i < K && !first; ++i) first = orig[0][i];
-        for (unsigned i = 0; i < R && !first; ++i) first = rec[0][i];
         MemKind k16 = MemKind::Host;
-        const int d16 = pick_device(first, &k16);
+        const int d16 = pick_device(first_piece(K, R, orig[0], rec[0]), &k16);  // the device rule of decode_any
         if (k16 == MemKind::Device) {
             RangeCache rc;
             bool on_dev = true;
@@ -4073,8 +4077,7 @@ LEO_EXPORT LeopardResult leo_decode(uint64_t buffer_bytes, unsigned original_cou
 LEO_EXPORT LeopardResult leo_amd_encode_slice(uint64_t buffer_bytes, uint64_t byte_offset, uint64_t slice_bytes,
                                               unsigned original_count, unsigned recovery_count, unsigned work_count,
                                               const void* const* const original_data, void** work_data) {
-    if (slice_bytes == 0 || slice_bytes % 64 || byte_offset % 64 || byte_offset + slice_bytes > buffer_bytes)
-        return Leopard_InvalidSize;
+    if (!check_slice(buffer_bytes, byte_offset, slice_bytes)) return Leopard_InvalidSize;
     LeopardResult r = check_encode(buffer_bytes, original_count, recovery_count, work_count, original_data, work_data);
     if (r != Leopard_Success) return r;
     return encode_any(slice_bytes, byte_offset, original_count, recovery_count, original_data, work_data);
@@ -4084,8 +4087,7 @@ LEO_EXPORT LeopardResult leo_amd_decode_slice(uint64_t buffer_bytes, uint64_t by
                                               unsigned original_count, unsigned recovery_count, unsigned work_count,
                                               const void* const* const original_data,
                                               const void* const* const recovery_data, void** work_data) {
-    if (slice_bytes == 0 || slice_bytes % 64 || byte_offset % 64 || byte_offset + slice_bytes > buffer_bytes)
-        return Leopard_InvalidSize;
+    if (!check_slice(buffer_bytes, byte_offset, slice_bytes)) return Leopard_InvalidSize;
     LeopardResult r = check_decode(buffer_bytes, original_count, recovery_count, work_count, original_data,
                                    recovery_data, work_data);
     if (r != Leopard_Success) return r;
@@ -4108,8 +4110,7 @@ LEO_EXPORT LeopardResult leo_amd_update_slice(uint64_t buffer_bytes, uint64_t by
                                               unsigned original_count, unsigned recovery_count,
                                               unsigned changed_count, const unsigned* changed_index,
                                               const void* const* delta_data, void** recovery_data) {
-    if (slice_bytes == 0 || slice_bytes % 64 || byte_offset % 64 || byte_offset + slice_bytes > buffer_bytes)
-        return Leopard_InvalidSize;
+    if (!check_slice(buffer_bytes, byte_offset, slice_bytes)) return Leopard_InvalidSize;
     bool nothing = false;
     LeopardResult r = check_update(buffer_bytes, original_count, recovery_count, changed_count, changed_index,
                                    delta_data, recovery_data, &nothing);
@@ -4147,8 +4148,7 @@ LEO_EXPORT LeopardResult leo_amd_repair_slice(uint64_t buffer_bytes, uint64_t by
                                               unsigned original_count, unsigned recovery_count, unsigned work_count,
                                               const void* const* original_data, const void* const* recovery_data,
                                               void** work_data, void** recovery_out) {
-    if (slice_bytes == 0 || slice_bytes % 64 || byte_offset % 64 || byte_offset + slice_bytes > buffer_bytes)
-        return Leopard_InvalidSize;
+    if (!check_slice(buffer_bytes, byte_offset, slice_bytes)) return Leopard_InvalidSize;
     const LeopardResult r =
         check_repair(buffer_bytes, original_count, recovery_count, original_data, recovery_data, work_data, recovery_out);
     if (r != Leopard_Success) return r;
@@ -4179,8 +4179,7 @@ LEO_EXPORT LeopardResult leo_amd_verify_slice(uint64_t buffer_bytes, uint64_t by
                                               unsigned original_count, unsigned recovery_count,
                                               const void* const* original_data, const void* const* recovery_data,
                                               uint32_t* mismatch, unsigned* mismatch_count) {
-    if (slice_bytes == 0 || slice_bytes % 64 || byte_offset % 64 || byte_offset + slice_bytes > buffer_bytes)
-        return Leopard_InvalidSize;
+    if (!check_slice(buffer_bytes, byte_offset, slice_bytes)) return Leopard_InvalidSize;
     const LeopardResult r =
         check_verify(buffer_bytes, original_count, recovery_count, original_data, recovery_data, mismatch_count);
     if (r != Leopard_Success) return r;
